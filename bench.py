@@ -3,7 +3,7 @@
 scored/s) on an ML-20M-shaped synthetic interaction set, k = 64, fp32 tables (BASELINE.json
 configs[1]), hogwild (throughput) mode — the counterpart of the reference's OpenMP path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one BPR epoch (nnz = 20 000 263 sampled triplets) over the resident interaction
 matrix.  For N > 1 the driver launches this file under torch.distributed.run, one rank per GPU;
@@ -13,10 +13,12 @@ table is reconciled by RCCL all-reduce of its deltas (cornac_amd/dist.py).
 A plain `python bench.py --gpus N` (no WORLD_SIZE in the environment) re-executes itself under
 torch.distributed.run with N ranks on 127.0.0.1, so the one command works with and without an external launcher.
 
-At N = 1 the line also carries `legs`: the other single-GPU configurations of BASELINE.json, each with its own
-`roofline` and reference `cpu_baseline` — `mf_netflix` / `wmf_netflix` (configs[2]: biased MF and WMF, k = 128, at the
-Netflix Prize shape),
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does not
+need: the scoring leg (`rank`), the reference `cpu_baseline` and, at N = 1, `legs`: the other single-GPU configurations
+of BASELINE.json, each with its own `roofline` and reference `cpu_baseline` — `mf_netflix` / `wmf_netflix` (configs[2]:
+biased MF and WMF, k = 128, at the Netflix Prize shape),
 `vbpr_tradesy` (configs[3]) and `bpr_k128_scale` (one GPU's user slice of configs[4], k = 128).
+`--dump-outputs DIR` writes reproducible outputs of the timed epoch for output-for-output comparisons (see dump_outputs).
 
 Rank 0 prints ONE JSON line (see README / DESIGN.md "Measurement" for every field).
 """
@@ -113,6 +115,38 @@ def init_factors(n_users, n_items, k, seed):
     U = ((rng.uniform(0, 1, (n_users, k)).astype(np.float32) - 0.5) / k)
     V = ((rng.uniform(0, 1, (n_items, k)).astype(np.float32) - 0.5) / k)
     return U, V, np.zeros(n_items, np.float32)
+
+
+DUMP_BYTES = 63 * 10 ** 6  # the tables' share of the 64 MB a dump may take (the rest: .npy headers, counters)
+DUMP_MT_SEEDS = (0xC0FFEE, 0xC0FFEF)  # the two mt19937 streams of the deterministic epoch --dump-outputs writes
+
+
+def dump_outputs(out_dir, trainer, U0, V0, B0, lr, reg, last_skipped):
+    """--dump-outputs, after the timed steps and outside the timing.  A hogwild epoch's tables and `correct` count depend
+    on the order in which concurrent updates land (two runs from identical tables differ in every element after one
+    epoch), so they cannot be compared run to run.  Written instead, the same on every run with the same arguments:
+      last_step_skipped  the last timed step's skipped draws (seeded sampler, bin deal, membership probes);
+      u_factors, i_factors, i_biases, correct_skipped  the same epoch - this handle, data, k, lr, reg and bias - in the
+          library's deterministic mode (every update observes all earlier ones) from the tables the timed loop started
+          from: what the SGD arithmetic makes of them.
+    Tables are float32, counters float64.  Over DUMP_BYTES in all, every table keeps the same fraction of its rows,
+    drawn with a fixed seed per row count (i_factors and i_biases keep the same rows).  Leaves the handle trained."""
+    from cornac_amd import _lib
+
+    trainer.set_factors(U0, V0, B0)
+    trainer.seed_mt19937(*DUMP_MT_SEEDS)
+    c, s = trainer.fit_epochs(1, lr, reg, True, _lib.NEG_UNIFORM, _lib.MODE_DETERMINISTIC)
+    U, V, B = trainer.get_factors()
+    tables = {"u_factors": U, "i_factors": V, "i_biases": B}
+    os.makedirs(out_dir, exist_ok=True)
+    frac = min(1.0, DUMP_BYTES / float(sum(t.nbytes for t in tables.values())))
+    for name, t in tables.items():
+        if frac < 1.0:
+            n = len(t)
+            t = t[np.sort(np.random.RandomState(n).choice(n, max(1, int(n * frac)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), t)
+    np.save(os.path.join(out_dir, "correct_skipped.npy"), np.array([c, s], np.float64))
+    np.save(os.path.join(out_dir, "last_step_skipped.npy"), np.array([last_skipped], np.float64))
 
 
 def cpu_baseline_reference(indptr, indices, n_items, k, lr, reg, budget_s):
@@ -1008,8 +1042,26 @@ def main():
     ap.add_argument("--legs", default="mf_netflix,wmf_netflix,vbpr_tradesy,bpr_k128_scale,dist_tax",
                     help="extra single-GPU legs reported under `legs` at N = 1 (comma list; empty = none)")
     ap.add_argument("--no-legs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the scoring leg (`rank`), the extra legs and the CPU "
+                         "baselines (--no-rank, --no-legs and --cpu-baseline-seconds select among them); a plain run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write outputs that are the same on every run with the same arguments as "
+                         "DIR/<name>.npy: the last step's skipped draws, and the trained tables and counters of the same epoch "
+                         "in the library's deterministic mode from the tables the timed loop started from (the hogwild "
+                         "tables depend on the order in which concurrent updates land; see dump_outputs).  Single-process "
+                         "GPU path only")
     ap.add_argument("--dry-run-cpu", action="store_true", help="launcher / timing scaffolding only, gloo, no GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist or args.dry_run_cpu):
+        ap.error("--dump-outputs needs the single-process GPU path: the multi-GPU runners count skipped draws per exchange, "
+                 "not per step, and the dry run trains nothing")
+    if not args.full:
+        args.no_rank = args.no_legs = True
+        args.cpu_baseline_seconds = 0.0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)  # does not return
     if args.dry_run_cpu:
@@ -1127,6 +1179,7 @@ def main():
         step_ms.append(1e3 * (time.perf_counter() - ts))
         correct += c
         skipped += s
+    last_skipped = s
     if sharded is not None:
         correct, skipped = sharded.finish()
     barrier()
@@ -1285,6 +1338,8 @@ def main():
             except Exception as e:
                 print("[bench] rank cpu_baseline failed: %r" % (e,), file=sys.stderr)
                 out["rank"]["cpu_baseline"] = None
+    if args.dump_outputs:  # (after the scoring leg, which ranks the hogwild-trained tables)
+        dump_outputs(args.dump_outputs, trainer, U, V, B, args.lr, args.reg, last_skipped)
     trainer.close()
 
     # ---- extra single-GPU legs (rank 0, N = 1 only) -------------------------------------------------------------

@@ -32,3 +32,13 @@ def test_gpus_2_spawns_two_ranks_and_reports_the_slowest():
     # rank 1's stand-in step sleeps twice as long as rank 0's: the line must carry the slower rank's time
     assert d["ms_per_step"] >= 3.5, d
     assert abs(d["value"] - 1000.0 * 4 * 2 / (d["ms_per_step"] * 4 / 1e3)) < 1e-6 * d["value"]
+
+
+def test_dump_outputs_is_refused_where_a_step_has_no_counters_of_its_own():
+    """--dump-outputs writes the last step's skipped draws and a deterministic epoch of the trainer: the multi-GPU runners
+    count per exchange, not per step, and the dry run trains nothing"""
+    for extra in (["--gpus", "2"], ["--force-dist"], []):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "unused", "--dry-run-cpu"] + extra,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert out.returncode == 2 and "--dump-outputs needs the single-process GPU path" in out.stderr, out.stderr[-2000:]
+        assert not os.path.exists("unused")

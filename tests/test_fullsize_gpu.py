@@ -1,5 +1,7 @@
 """Parity and properties at BASELINE.json's full size (configs[1]: ML-20M shape, k = 64)."""
+import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -57,6 +59,40 @@ def test_deterministic_full_epoch_matches_sequential_oracle(oracle, ml20m):
     print("full-size deterministic epoch: max |err| = %.3g, timing %s" % (err, timing))
     assert err <= 1e-4
     assert np.mean(Ud == U) > 0.99, "expected (almost) bit-identical user factors"
+
+
+def test_bench_dump_outputs_are_the_same_on_every_run(tmp_path, ml20m):
+    """`bench.py --dump-outputs` with one timed step: two runs write the same files; last_step_skipped is the timed step's
+    count (the JSON line's); the tables and counters are the deterministic epoch from the bench's initial tables (the same
+    epoch run here on a fresh handle), and the SGD moved every table"""
+    from bench import DUMP_MT_SEEDS, init_factors
+
+    n_users, n_items, indptr, indices, _ = ml20m
+    names = ["correct_skipped", "i_biases", "i_factors", "last_step_skipped", "u_factors"]
+    runs = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert sorted(f[:-len(".npy")] for f in os.listdir(str(tmp_path / d))) == names
+        runs.append((line, {n: np.load(str(tmp_path / d / (n + ".npy"))) for n in names}))
+    (line, a), (_, b) = runs
+    assert all(a[n].dtype == b[n].dtype and a[n].tobytes() == b[n].tobytes() for n in names)
+    assert a["last_step_skipped"].dtype == np.float64 and a["last_step_skipped"].shape == (1,)
+    assert abs(a["last_step_skipped"][0] - line["train_stats"]["skipped_frac"] * len(indices)) < 0.5
+    U0, V0, B0 = init_factors(n_users, n_items, 64, 100)
+    tr = _lib.BprTrainer(indptr, indices, n_users, n_items, n_users, n_items, 64)
+    tr.set_factors(U0, V0, B0)
+    tr.seed_mt19937(*DUMP_MT_SEEDS)
+    c, s = tr.fit_epochs(1, 0.05, 0.01, True, _lib.NEG_UNIFORM, _lib.MODE_DETERMINISTIC)
+    want = dict(zip(("u_factors", "i_factors", "i_biases"), tr.get_factors()))
+    tr.close()
+    assert a["correct_skipped"].dtype == np.float64 and list(a["correct_skipped"]) == [c, s]
+    for n, start in (("u_factors", U0), ("i_factors", V0), ("i_biases", B0)):
+        assert a[n].dtype == np.float32 and a[n].shape == want[n].shape and np.array_equal(a[n], want[n]), n
+        assert np.mean(a[n] != start) > 0.9, n
 
 
 @pytest.mark.parametrize("form", ["ldsbin", "fused"])
