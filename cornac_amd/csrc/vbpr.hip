@@ -750,8 +750,13 @@ int cornac_hip_vbpr_item_tables(cornac_hip_vbpr_t h, float *theta_item, float *v
         th.alloc((size_t)h->n_items * h->k2);
         vb.alloc((size_t)h->n_items);
         const VbprTables t = vb_tables(h);
-        hipLaunchKernelGGL(vbpr_item_tables_kernel, dim3((unsigned)h->n_items), dim3(kVb),
-                           (size_t)(h->n_feat + kVb) * sizeof(float), h->stream, t, th.p, vb.p);
+        // one feature row in LDS: above 64 KB when n_feat > 16128 (create() admits up to 160 KB), so the kernel's
+        // dynamic-LDS limit is raised as for the library's other large-LDS launches (tests/test_vbpr_gpu.py runs this at
+        // n_feat 20 000 and at the create bound)
+        const size_t lds = (size_t)(h->n_feat + kVb) * sizeof(float);
+        HIP_CHECK(hipFuncSetAttribute((const void *)vbpr_item_tables_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)lds));
+        hipLaunchKernelGGL(vbpr_item_tables_kernel, dim3((unsigned)h->n_items), dim3(kVb), lds, h->stream, t, th.p, vb.p);
         HIP_CHECK(hipGetLastError());
         th.download(theta_item, th.n, h->stream);
         vb.download(visual_bias, vb.n, h->stream);

@@ -123,3 +123,63 @@ def timed_steps(features, params, u, i, j, batch_size, lr=0.005, lambda_w=0.01, 
     if return_params:
         return n, time.time() - t0, {name: t.detach().numpy().copy() for name, t in P.items()}
     return n, time.time() - t0
+
+
+TABLES = ("Bi", "Gu", "Gi", "Tu", "E", "Bp")
+
+
+def steps_f64(features, params, batches, lr, lambda_w, lambda_b, lambda_e, skip=None):
+    """The minibatch step of VBPROracle.fit (recom_vbpr.py:242-262) in float64 over an explicit list of batches — the
+    checker of the device's step at shapes and schedules the sampler never produces (ragged, tiny, i == j, ...).
+
+    `batches` is a list of (u, i, j) arrays of any lengths; each batch is one Adam step and all of them form ONE
+    continuing sequence (a device handle keeps Adam's step count across calls, so several calls equal one run over the
+    concatenated list).  The gradient is torch autograd's; Adam is written out (torch.optim.Adam's single-tensor formula,
+    dense: every row's moments decay, and a row with m = v = 0 stays exactly where it is) so that `skip = (table, row,
+    t)` can withhold the update of one row of one table at batch index t (0-based) — the sensitivity control of the
+    device tests.  `params` maps Bi, Gu, Gi, Tu, E, Bp to arrays (Bp of n_feat entries in any shape).
+    Returns ({name: float64 table, Bp as a vector}, [NLL of every step]) with NLL = -sum logsigmoid(X) over the B x B
+    broadcast entries (the device's `sum_nll`)."""
+    import torch
+
+    dt = torch.float64
+    F = torch.tensor(np.asarray(features, np.float64))
+    P = {n: torch.tensor(np.asarray(params[n], np.float64).reshape(-1, 1) if n == "Bp" else
+                         np.asarray(params[n], np.float64), dtype=dt) for n in TABLES}
+    M = {n: torch.zeros_like(P[n]) for n in TABLES}
+    V = {n: torch.zeros_like(P[n]) for n in TABLES}
+    b1, b2, eps = 0.9, 0.999, 1e-8
+
+    def l2(*ts):
+        return sum(t.pow(2).sum() for t in ts) / 2
+
+    nll = []
+    for t, (u, i, j) in enumerate(batches):
+        bu, bi, bj = (torch.as_tensor(np.asarray(x, np.int64)) for x in (u, i, j))
+        L = {n: P[n].clone().requires_grad_(True) for n in TABLES}
+        Bi, Gu, Gi, Tu, E, Bp = (L[n] for n in TABLES)
+        gu, tu = Gu[bu], Tu[bu]
+        beta_i, beta_j = Bi[bi], Bi[bj]
+        gi, gj = Gi[bi], Gi[bj]
+        feat_diff = F[bi] - F[bj]
+        # [B] + [B, 1]: the reference's B x B broadcast score
+        X = (beta_i - beta_j + (gu * (gi - gj)).sum(dim=1) + (tu * feat_diff.mm(E)).sum(dim=1) + feat_diff.mm(Bp))
+        ll = torch.nn.functional.logsigmoid(X).sum()
+        loss = -ll + (l2(gu, gi, gj, tu) * lambda_w + l2(beta_i) * lambda_b + l2(beta_j) * lambda_b / 10
+                      + l2(E, Bp) * lambda_e)
+        grads = torch.autograd.grad(loss, [L[n] for n in TABLES])
+        nll.append(-float(ll.detach()))
+        step = t + 1
+        step_size = lr / (1 - b1 ** step)
+        bc2_sqrt = (1 - b2 ** step) ** 0.5
+        for n, g in zip(TABLES, grads):
+            p, m, v = P[n], M[n], V[n]
+            keep = None
+            if skip is not None and skip[0] == n and skip[2] == t:
+                keep = (p[skip[1]].clone(), m[skip[1]].clone(), v[skip[1]].clone())
+            m.lerp_(g, 1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
+            p.addcdiv_(m, (v.sqrt() / bc2_sqrt).add_(eps), value=-step_size)
+            if keep is not None:
+                p[skip[1]], m[skip[1]], v[skip[1]] = keep
+    return {n: (P[n].reshape(-1) if n == "Bp" else P[n]).numpy().copy() for n in TABLES}, nll
