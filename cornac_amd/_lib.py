@@ -19,8 +19,13 @@ CSRC = os.path.join(_HERE, "csrc")
 MODE_DETERMINISTIC = 0
 MODE_HOGWILD = 1
 VEBPR_NO_OWNERSHIP = 0x100
-# hogwild_flags bits 16..19: the form of a whole-epoch hogwild call (include/cornac_hip.h)
-FORM_AUTO, FORM_FUSED, FORM_STRATA, FORM_LDSBIN = 0, 1 << 16, 2 << 16, 3 << 16
+# hogwild_flags (include/cornac_hip.h, CORNAC_HIP_HOG_* / CORNAC_HIP_FORM_*): the form field of a hogwild call ...
+HOG_FORM_MASK, HOG_FORM_SHIFT = 0xF0000, 16
+FORM_AUTO, FORM_FUSED, FORM_STRATA, FORM_LDSBIN = (f << HOG_FORM_SHIFT for f in range(4))
+# ... the switches below it (bit 5, value 32, is reserved) and the ablation field of the profile build
+HOG_PLAIN_STORES, HOG_VEC4_LAYOUT, HOG_NO_OWNERSHIP, HOG_DENSE_BIAS, HOG_SHARE_NEG = 1, 2, 4, 8, 16
+HOG_BINNED, HOG_FUSED_OPT_OUT = 64, 128
+HOG_ABLATE_MASK, HOG_ABLATE_SHIFT = 0xFF00, 8
 NEG_UNIFORM = 0
 NEG_POPULARITY = 1
 

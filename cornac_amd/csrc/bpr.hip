@@ -681,7 +681,7 @@ struct cornac_hip_bpr {
     DevBuf<float> Bpad;  // hogwild-mode view of B, one bias per 128-byte line
     // XCD-strata form inside fit_epochs: ONE record per item — the row (padded to whole 128-byte lines) with its bias line
     // behind it — so that a triplet names 3 random locations instead of 5.  While strata_packed is set the records are
-    // authoritative and the dense V / B are stale; every other entry point unpacks first (bpr_check).
+    // authoritative and the dense V / B are stale; every other entry point unpacks first (bpr_check, PackedRecords).
     DevBuf<float> VB;
     bool strata_packed = false, strata_allow_pack = false;
     bool chunk_records = false;  // cornac_hip_bpr_chunk_records: the chunk API may keep the records too (multi-GPU driver)
@@ -775,17 +775,36 @@ struct cornac_hip_bpr {
 
 static constexpr int64_t kDetChunk = int64_t(1) << 24;
 
-static void strata_unpack(cornac_hip_bpr_t h);
-// every entry point that may read or write the dense tables goes through here: packed strata records are written back
-static void bpr_check(cornac_hip_bpr_t h) {
-    REQUIRE(h != nullptr, "BPR handle is NULL");
-    HIP_CHECK(hipSetDevice(h->device));
-    if (h->strata_packed) strata_unpack(h);
+// ---- packed item records of the XCD-strata form (the handle's VB; kernels in bpr_strata.inc) --------------------
+static void strata_pack(cornac_hip_bpr_t h) {
+    if (h->strata_packed) return;
+    h->vb_kp = (h->k + kBiasStride - 1) / kBiasStride * kBiasStride;
+    h->vb_pitch = h->vb_kp + kBiasStride;
+    h->VB.ensure((size_t)h->total_items * h->vb_pitch);
+    const int64_t n = (int64_t)h->total_items * h->vb_pitch;
+    hipLaunchKernelGGL(strata_pack_kernel, dim3((unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536)), dim3(kBlock), 0,
+                       h->stream, h->V.p, h->B.p, h->total_items, h->k, h->vb_kp, h->vb_pitch, h->VB.p);
+    HIP_CHECK(hipGetLastError());
+    h->strata_packed = true;
 }
-// ... except the epoch loop of fit_epochs, which keeps them across calls
-static void bpr_check_keep_packed(cornac_hip_bpr_t h) {
+
+static void strata_unpack(cornac_hip_bpr_t h) {
+    if (!h->strata_packed) return;
+    const int64_t n = (int64_t)h->total_items * h->k;
+    hipLaunchKernelGGL(strata_unpack_kernel, dim3((unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536)), dim3(kBlock), 0,
+                       h->stream, h->VB.p, h->total_items, h->k, h->vb_kp, h->vb_pitch, h->V.p, h->B.p);
+    HIP_CHECK(hipGetLastError());
+    h->strata_packed = false;
+}
+
+// Every entry point starts here and says what it needs of the records: Records::Unpack — it may read or write the
+// dense tables, so packed records are written back first; Records::Keep — it touches no table, or works on the
+// records themselves (the hogwild entry points, which then decide through PackedRecords, and the table_delta passes).
+enum class Records { Unpack, Keep };
+static void bpr_check(cornac_hip_bpr_t h, Records records) {
     REQUIRE(h != nullptr, "BPR handle is NULL");
     HIP_CHECK(hipSetDevice(h->device));
+    if (records == Records::Unpack) strata_unpack(h);
 }
 
 extern "C" {
@@ -855,7 +874,7 @@ int cornac_hip_bpr_destroy(cornac_hip_bpr_t h) {
 
 int cornac_hip_bpr_set_factors(cornac_hip_bpr_t h, const float *U, const float *V, const float *B) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         h->f64 = false;
         if (U) h->U.upload(U, (size_t)h->total_users * h->k, h->stream);
         if (V) h->V.upload(V, (size_t)h->total_items * h->k, h->stream);
@@ -866,7 +885,7 @@ int cornac_hip_bpr_set_factors(cornac_hip_bpr_t h, const float *U, const float *
 
 int cornac_hip_bpr_get_factors(cornac_hip_bpr_t h, float *U, float *V, float *B) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(!h->f64, "the handle holds float64 tables (use cornac_hip_bpr_get_factors_f64)");
         if (U) h->U.download(U, (size_t)h->total_users * h->k, h->stream);
         if (V) h->V.download(V, (size_t)h->total_items * h->k, h->stream);
@@ -877,7 +896,7 @@ int cornac_hip_bpr_get_factors(cornac_hip_bpr_t h, float *U, float *V, float *B)
 
 int cornac_hip_bpr_set_factors_f64(cornac_hip_bpr_t h, const double *U, const double *V, const double *B) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(U && V && B, "float64 tables are set together (the reference's fused type is one type for U, V and B)");
         h->U64.ensure((size_t)h->total_users * h->k);
         h->V64.ensure((size_t)h->total_items * h->k);
@@ -891,7 +910,7 @@ int cornac_hip_bpr_set_factors_f64(cornac_hip_bpr_t h, const double *U, const do
 }
 int cornac_hip_bpr_get_factors_f64(cornac_hip_bpr_t h, double *U, double *V, double *B) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->f64, "the handle holds float32 tables (use cornac_hip_bpr_get_factors)");
         if (U) h->U64.download(U, (size_t)h->total_users * h->k, h->stream);
         if (V) h->V64.download(V, (size_t)h->total_items * h->k, h->stream);
@@ -901,7 +920,7 @@ int cornac_hip_bpr_get_factors_f64(cornac_hip_bpr_t h, double *U, double *V, dou
 }
 int cornac_hip_bpr_bind_device(cornac_hip_bpr_t h, float *dU, float *dV, float *dB) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         if (dU) h->U.bind(dU, (size_t)h->total_users * h->k);
         if (dV) h->V.bind(dV, (size_t)h->total_items * h->k);
@@ -911,7 +930,7 @@ int cornac_hip_bpr_bind_device(cornac_hip_bpr_t h, float *dU, float *dV, float *
 
 int cornac_hip_bpr_set_negative_population(cornac_hip_bpr_t h, const int32_t *items, int64_t n) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && n < (int64_t(1) << 32), "population size out of range");
         REQUIRE(n == 0 || items != nullptr, "items is NULL");
         for (int64_t t = 0; t < n; ++t)
@@ -928,7 +947,7 @@ int cornac_hip_bpr_set_negative_population(cornac_hip_bpr_t h, const int32_t *it
 
 int cornac_hip_bpr_rebind_items(cornac_hip_bpr_t h, float *dV, float *dB) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(dV && dB, "NULL device pointer");
         REQUIRE(!h->V.owned && !h->B.owned, "the item tables are the handle's own: bind caller-owned ones first "
                 "(cornac_hip_bpr_bind_device); rebind_items only swaps them");
@@ -941,7 +960,7 @@ int cornac_hip_bpr_rebind_items(cornac_hip_bpr_t h, float *dV, float *dB) {
 
 int cornac_hip_bpr_device_ptrs(cornac_hip_bpr_t h, float **dU, float **dV, float **dB) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         if (dU) *dU = h->U.p;
         if (dV) *dV = h->V.p;
         if (dB) *dB = h->B.p;
@@ -950,7 +969,7 @@ int cornac_hip_bpr_device_ptrs(cornac_hip_bpr_t h, float **dU, float **dV, float
 
 int cornac_hip_bpr_set_stream(cornac_hip_bpr_t h, void *hip_stream) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     });
@@ -958,7 +977,7 @@ int cornac_hip_bpr_set_stream(cornac_hip_bpr_t h, void *hip_stream) {
 
 int cornac_hip_bpr_switch_stream(cornac_hip_bpr_t h, void *hip_stream) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     });
 }
@@ -970,7 +989,7 @@ static void mt_init_genrand(uint32_t seed, uint32_t *mt) {
 
 int cornac_hip_bpr_seed_mt19937(cornac_hip_bpr_t h, uint32_t mt_seed_pos, uint32_t mt_seed_neg, int shared_stream) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         std::vector<uint32_t> st(2 * MT_N);
         mt_init_genrand(mt_seed_pos, st.data());
         mt_init_genrand(mt_seed_neg, st.data() + MT_N);
@@ -989,7 +1008,7 @@ int cornac_hip_bpr_seed_mt19937(cornac_hip_bpr_t h, uint32_t mt_seed_pos, uint32
 
 int cornac_hip_bpr_seed_hogwild(cornac_hip_bpr_t h, uint64_t seed) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (touches no table: packed strata records stay)
+        bpr_check(h, Records::Keep);  // (touches no table: packed strata records stay)
         h->hog_seed = seed;
         h->hog_epoch = 0;
         h->hog_offset = 0;
@@ -1145,15 +1164,15 @@ typedef void (*HogKernel)(const HogArgs);
 
 template <bool ATOMIC>
 static HogKernel pick_hogwild_kernel(int k, int flags) {
-    const bool vec4_layout = (flags & 2) != 0;  // experiment switch: the float4-per-lane layout
+    const bool vec4_layout = (flags & CORNAC_HIP_HOG_VEC4_LAYOUT) != 0;  // experiment switch: the float4-per-lane layout
     if (!vec4_layout && k <= 256) {
-        const bool owned = ATOMIC && (flags & 4) == 0 && k > 32;  // bit2 disables user-row ownership
+        const bool owned = ATOMIC && (flags & CORNAC_HIP_HOG_NO_OWNERSHIP) == 0 && k > 32;
         if (k <= 4) return bpr_hogwild_rowwise_kernel<4, 1, 2, ATOMIC, false>;
         if (k <= 8) return bpr_hogwild_rowwise_kernel<8, 1, 2, ATOMIC, false>;
         if (k <= 16) return bpr_hogwild_rowwise_kernel<16, 1, 2, ATOMIC, false>;
         if (k <= 32) return bpr_hogwild_rowwise_kernel<32, 1, 4, ATOMIC, false>;
         if (owned) {
-            if (k <= 64 && (flags & 16)) return bpr_hogwild_rowwise_kernel<64, 1, 4, true, true, 0, true>;  // experiment
+            if (k <= 64 && (flags & CORNAC_HIP_HOG_SHARE_NEG)) return bpr_hogwild_rowwise_kernel<64, 1, 4, true, true, 0, true>;  // experiment
             if (k <= 64) return bpr_hogwild_rowwise_kernel<64, 1, 4, true, true>;
             if (k <= 128) return bpr_hogwild_rowwise_kernel<64, 2, 2, true, true>;
             if (k <= 192) return bpr_hogwild_rowwise_kernel<64, 3, 2, true, true>;
@@ -1258,10 +1277,10 @@ static void build_ownership(cornac_hip_bpr_t h, int64_t W) {
 }
 
 static bool hogwild_uses_ownership(cornac_hip_bpr_t h, int flags) {
-    // bit0 plain stores, bit1 float4 layout, bit2 explicit opt-out; needs one triplet per wave step
-    // (k > 32) and at least one 64-sample tile per wave and epoch
-    flags &= ~8;  // bit3 (dense bias) is independent of ownership
-    if ((flags & 7) != 0 || h->k <= 32 || h->k > 256) return false;  // bits >= 8 are profiling ablations
+    // not with plain stores, the float4 layout or the explicit opt-out (the dense bias table and the ablation field are
+    // independent of it); needs one triplet per wave step (k > 32) and at least one 64-sample tile per wave and epoch
+    constexpr int kUnowned = CORNAC_HIP_HOG_PLAIN_STORES | CORNAC_HIP_HOG_VEC4_LAYOUT | CORNAC_HIP_HOG_NO_OWNERSHIP;
+    if ((flags & kUnowned) != 0 || h->k <= 32 || h->k > 256) return false;
     const int64_t W = (int64_t)device_info(h->device).cus * 8 * kWavesPerBlock;
     return h->nnz >= W * kWave;
 }
@@ -1269,8 +1288,8 @@ static bool hogwild_uses_ownership(cornac_hip_bpr_t h, int flags) {
 static void launch_hogwild(cornac_hip_bpr_t h, HogArgs a, int flags) {
     const DeviceInfo &di = device_info(h->device);
     const bool owned = hogwild_uses_ownership(h, flags);
-    if (!owned) flags |= 4;
-    HogKernel kern = (flags & 1) ? pick_hogwild_kernel<false>(h->k, flags) : pick_hogwild_kernel<true>(h->k, flags);
+    if (!owned) flags |= CORNAC_HIP_HOG_NO_OWNERSHIP;
+    HogKernel kern = (flags & CORNAC_HIP_HOG_PLAIN_STORES) ? pick_hogwild_kernel<false>(h->k, flags) : pick_hogwild_kernel<true>(h->k, flags);
     // persistent grid: exactly the number of workgroups that are co-resident, so the tile loop of
     // every wave starts at once (no second dispatch round with a ragged tail)
     if (h->hog_kernel != kern) {
@@ -1360,11 +1379,10 @@ static void build_item_buckets(cornac_hip_bpr_t h, int n_buckets, int neg_popula
     h->bin_hot_threshold = hot_threshold;
 }
 
-static int env_int(const char *name, int dflt) { return prof_env_int(name, dflt); }  // profile builds only
 typedef void (*BinTripletKernel)(const HogArgs, const BinArgs);
 typedef void (*BinApplyKernel)(const BinApplyArgs);
 static void pick_binned_kernels(int k, int occ, BinTripletKernel *ka, BinApplyKernel *kb) {
-    if (k <= 64) { *ka = occ >= 2 ? bpr_binned_triplet_kernel<1, 4, 2> : env_int("CORNAC_HIP_BIN_UNRA", 4) >= 8 ? bpr_binned_triplet_kernel<1, 8, 1> : bpr_binned_triplet_kernel<1, 4, 1>; *kb = env_int("CORNAC_HIP_BIN_UNRB", 4) >= 4 ? bpr_binned_apply_kernel<1, 4> : bpr_binned_apply_kernel<1, 2>; }
+    if (k <= 64) { *ka = occ >= 2 ? bpr_binned_triplet_kernel<1, 4, 2> : prof_env_int("CORNAC_HIP_BIN_UNRA", 4) >= 8 ? bpr_binned_triplet_kernel<1, 8, 1> : bpr_binned_triplet_kernel<1, 4, 1>; *kb = prof_env_int("CORNAC_HIP_BIN_UNRB", 4) >= 4 ? bpr_binned_apply_kernel<1, 4> : bpr_binned_apply_kernel<1, 2>; }
     else if (k <= 128) { *ka = occ >= 2 ? bpr_binned_triplet_kernel<2, 2, 2> : bpr_binned_triplet_kernel<2, 2, 1>; *kb = bpr_binned_apply_kernel<2, 2>; }
     else if (k <= 192) { *ka = bpr_binned_triplet_kernel<3, 2, 1>; *kb = bpr_binned_apply_kernel<3, 1>; }
     else { *ka = bpr_binned_triplet_kernel<4, 1, 1>; *kb = bpr_binned_apply_kernel<4, 1>; }
@@ -1383,10 +1401,9 @@ struct BinPlan {
     int cap = 0;  // messages per segment (a multiple of 64)
     int hot_threshold = 0;
 };
-static BinPlan plan_binned(cornac_hip_bpr_t h, int flags, float lr) {
+static BinPlan plan_binned(cornac_hip_bpr_t h) {
     BinPlan pl;
-    // opt-in (hogwild_flags bit 6): measured slower than the fused atomic kernel at the ML-20M shape
-    if ((flags & 0xff) != 64 || h->k <= 32 || h->k > 256) return pl;
+    if (h->k <= 32 || h->k > 256) return pl;
     const DeviceInfo &di = device_info(h->device);
     pl.n_buckets = di.cus;
     const int R = (h->k + kWave - 1) / kWave;
@@ -1396,7 +1413,7 @@ static BinPlan plan_binned(cornac_hip_bpr_t h, int flags, float lr) {
     BinTripletKernel ka;
     BinApplyKernel kb;
     if (h->bin_wg_per_cu == 0) {
-        const int want = std::max(1, std::min(2, env_int("CORNAC_HIP_BIN_WG_PER_CU", 1)));
+        const int want = std::max(1, std::min(2, prof_env_int("CORNAC_HIP_BIN_WG_PER_CU", 1)));
         pick_binned_kernels(h->k, want, &ka, &kb);
         int per_cu = 0;
         HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ka, kBinBlock, pl.lds_a));
@@ -1408,7 +1425,7 @@ static BinPlan plan_binned(cornac_hip_bpr_t h, int flags, float lr) {
     // Chunk length: every launch pays a pipeline fill/drain of about one tile per wave (measured ~0.16 ms), so chunks
     // should be few; every cold row receives up to hot_threshold updates computed from the chunk's start, so they
     // must not be long.  2 M triplets (a tenth of an ML-20M epoch) by default, never more than a quarter of an epoch.
-    const int64_t want = env_int("CORNAC_HIP_BIN_CHUNK", 0) > 0 ? env_int("CORNAC_HIP_BIN_CHUNK", 0) : (int64_t(1) << 21);
+    const int64_t want = prof_env_int("CORNAC_HIP_BIN_CHUNK", 0) > 0 ? prof_env_int("CORNAC_HIP_BIN_CHUNK", 0) : (int64_t(1) << 21);
     pl.chunk = std::max<int64_t>((int64_t)pl.grid_a * kBinWaves * kWave, std::min<int64_t>(want, h->nnz / 4));
     // a segment (bucket x producing workgroup) receives 2 chunk / (buckets x workgroups) messages on average: size
     // it for twice the mean (the surplus of an overflowing segment falls back to atomics)
@@ -1416,7 +1433,7 @@ static BinPlan plan_binned(cornac_hip_bpr_t h, int flags, float lr) {
     pl.cap = (int)std::min<int64_t>(1024, (2 * mean + kWave - 1) / kWave * kWave);
     // rows with more than hot_threshold messages per chunk keep device-scope atomics: the apply kernel serialises the
     // messages of one row (~250 cycles each under its lock), which must stay well below the kernel's duration
-    pl.hot_threshold = env_int("CORNAC_HIP_BIN_HOT", 0) > 0 ? env_int("CORNAC_HIP_BIN_HOT", 0) : 4096;
+    pl.hot_threshold = prof_env_int("CORNAC_HIP_BIN_HOT", 0) > 0 ? prof_env_int("CORNAC_HIP_BIN_HOT", 0) : 4096;
     pl.ok = true;
     return pl;
 }
@@ -1442,7 +1459,7 @@ static void fill_hog_args(cornac_hip_bpr_t h, HogArgs &a, int64_t n, float lr, f
     a.own_u = nullptr; a.own_i = nullptr; a.wave_ptr = nullptr; a.own_tmax = 0;
     a.xcd_claim = nullptr;
     a.nnz = h->nnz;
-    a.ablate = (flags >> 8) & 0xff;
+    a.ablate = (flags & CORNAC_HIP_HOG_ABLATE_MASK) >> CORNAC_HIP_HOG_ABLATE_SHIFT;
 }
 
 static void advance_hog_offset(cornac_hip_bpr_t h, int64_t n) {
@@ -1590,13 +1607,9 @@ static void build_item_ranks(cornac_hip_bpr_t h) {
     h->strata_code_waves = -1;
 }
 
-static bool hogwild_uses_strata(cornac_hip_bpr_t h, int64_t n_samples, int neg_population, int flags) {
-    const int form = (flags >> 16) & 15;  // 2 = asked for; 0 = automatic: item tables of >= 2^20 rows
-#ifdef CORNAC_PROFILE
-    flags &= ~0xff00;  // (profile builds: the ablation bits 8..15 are honoured by the strata kernel too)
-#endif
-    if ((flags & 0xffff) != 0 || !(form == 2 || (form == 0 && h->n_items >= (int64_t(1) << 20)))) return false;
-    (void)n_samples;  // any chunk of an epoch: a launch runs the partition phases that begin inside it
+// the shapes the strata form can run, whatever the flags (hog_form's predicate: ask hog_form).  Any chunk of an epoch: a
+// launch runs the partition phases that begin inside it
+static bool strata_can_run(cornac_hip_bpr_t h, int neg_population) {
     return neg_population == CORNAC_HIP_NEG_UNIFORM && hogwild_uses_ownership(h, 0) && h->n_items >= 64 &&
            device_info(h->device).xcds == 8;
 }
@@ -1647,27 +1660,6 @@ static void strata_build_buckets(cornac_hip_bpr_t h, int grid, uint32_t key) {
 // 8 phase launches per epoch, buckets re-dealt when the epoch key changes.  A chunk of an epoch (the multi-GPU driver's
 // exchange points) runs the phases whose nominal start p * nnz / 8 lies inside it, so consecutive chunks run every
 // phase of the epoch exactly once.
-static void strata_pack(cornac_hip_bpr_t h) {
-    if (h->strata_packed) return;
-    h->vb_kp = (h->k + kBiasStride - 1) / kBiasStride * kBiasStride;
-    h->vb_pitch = h->vb_kp + kBiasStride;
-    h->VB.ensure((size_t)h->total_items * h->vb_pitch);
-    const int64_t n = (int64_t)h->total_items * h->vb_pitch;
-    hipLaunchKernelGGL(strata_pack_kernel, dim3((unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536)), dim3(kBlock), 0,
-                       h->stream, h->V.p, h->B.p, h->total_items, h->k, h->vb_kp, h->vb_pitch, h->VB.p);
-    HIP_CHECK(hipGetLastError());
-    h->strata_packed = true;
-}
-
-static void strata_unpack(cornac_hip_bpr_t h) {
-    if (!h->strata_packed) return;
-    const int64_t n = (int64_t)h->total_items * h->k;
-    hipLaunchKernelGGL(strata_unpack_kernel, dim3((unsigned)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536)), dim3(kBlock), 0,
-                       h->stream, h->VB.p, h->total_items, h->k, h->vb_kp, h->vb_pitch, h->V.p, h->B.p);
-    HIP_CHECK(hipGetLastError());
-    h->strata_packed = false;
-}
-
 static void strata_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg, int use_bias, int flags) {
     const int grid = strata_prepare(h);
     // packed records only inside fit_epochs (strata_allow_pack) and only for tables the handle owns — or, in the chunk
@@ -1804,7 +1796,7 @@ static size_t ldsbin_lds_bytes(int cap, int k, int waves = kLbWaves) {
 //     is drawn, and its updates are exact LDS read-modify-writes; worth it when a row is drawn a few times per epoch
 //     (nnz >= lb_pass_min_draws_x100 / 100 x n_items), else the row traffic would exceed what the triplets need.
 struct LbPlan {
-    int bins = 0, block = kLbBlock, cap = 0;
+    int bins = 0, block = kLbBlock, cap = 0;  // bins: a multiple of the CU count; 0 = this shape does not use the form
     size_t lds = 0;
     bool passing = false;
 };
@@ -1872,15 +1864,9 @@ static LbPlan ldsbin_plan(cornac_hip_bpr_t h) {
     pl.passing = true;
     return pl;
 }
-// bins = a multiple of the CU count; 0 = this shape does not use the form
-static int ldsbin_plan_bins(cornac_hip_bpr_t h) { return ldsbin_plan(h).bins; }
 
-static bool hogwild_uses_ldsbin(cornac_hip_bpr_t h, int64_t n_samples, int neg_population, int flags) {
-    const int form = (flags >> 16) & 15;
-#ifdef CORNAC_PROFILE
-    flags &= ~0xff00;
-#endif
-    if (!(form == 0 || form == 3) || (flags & 0xffff) != 0) return false;
+// the launches the LDS-bin form can run, whatever the flags (hog_form's predicate: ask hog_form)
+static bool ldsbin_can_run(cornac_hip_bpr_t h, int64_t n_samples, int neg_population) {
     // uniform (BPR) and popularity-weighted (WBPR) negatives both have a binned form — the latter weights by the handle's
     // OWN interactions; a caller-supplied population (the global popularity of a multi-GPU fit) takes the fused kernel
     if (neg_population == CORNAC_HIP_NEG_POPULARITY && h->neg_pop_n) return false;
@@ -2020,7 +2006,7 @@ static void ldsbin_fill_args(cornac_hip_bpr_t h, LdsBinArgs &a, float lr, float 
     a.n_items = (int32_t)h->n_items; a.n_bins = h->lb_bins; a.n_hot = h->lb_n_hot; a.n_hot_inter = h->lb_n_hot_inter;
     a.bm_words = h->lb_bm_words; a.cap = h->lb_cap; a.n_strata = h->lb_n_strata;
     a.k = h->k; a.use_bias = use_bias; a.lr = lr; a.reg = reg;
-    a.ablate = ((flags >> 8) & 0xff) | (prof_env_int("CORNAC_HIP_LDSBIN_X", 0) << 8);
+    a.ablate = ((flags & CORNAC_HIP_HOG_ABLATE_MASK) >> CORNAC_HIP_HOG_ABLATE_SHIFT) | (prof_env_int("CORNAC_HIP_LDSBIN_X", 0) << 8);
     a.wg_clock = nullptr;
     a.ex = LdsBinExchange{};
     a.pre_rec = nullptr; a.pre_cnt = nullptr; a.pre_base = nullptr; a.pre_waves = 0;
@@ -2133,34 +2119,23 @@ static void ldsbin_resident_enqueue(cornac_hip_bpr_t h, float lr, float reg, int
     advance_hog_offset(h, h->nnz);
 }
 
-static void hogwild_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg, int use_bias,
-                            int neg_population, int flags) {
-    REQUIRE(h->hog_seeded, "hogwild mode needs cornac_hip_bpr_seed_hogwild first");
-    if (hogwild_uses_ldsbin(h, n_samples, neg_population, flags)) {
-        ldsbin_enqueue(h, n_samples, lr, reg, use_bias, neg_population, flags);
-        return;
-    }
-    if (hogwild_uses_strata(h, n_samples, neg_population, flags)) {
-        strata_enqueue(h, n_samples, lr, reg, use_bias, flags);
-        return;
-    }
-    flags &= 0xffff & ~128;  // bits 16..19 select the form, bit7 only opts out of the LDS-bin / strata forms
-    const BinPlan pl = plan_binned(h, flags, lr);
-    if (pl.ok) {
-        binned_enqueue(h, pl, n_samples, lr, reg, use_bias, neg_population, flags);
-        return;
-    }
-    flags &= ~(32 | 64);
-    if ((flags & 8) == 0) h->Bpad.ensure((size_t)h->total_items * kBiasStride);
+// ---- the fused kernel: every row update an atomic (or owned) write straight to the tables ----------------------------
+static void fused_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg, int use_bias, int neg_population,
+                          int flags) {
+    // what the fused kernels read: their experiment switches and the ablation field.  The form field, FUSED_OPT_OUT, a
+    // BINNED request that was turned down and the reserved bit 5 end here
+    flags &= CORNAC_HIP_HOG_PLAIN_STORES | CORNAC_HIP_HOG_VEC4_LAYOUT | CORNAC_HIP_HOG_NO_OWNERSHIP |
+             CORNAC_HIP_HOG_DENSE_BIAS | CORNAC_HIP_HOG_SHARE_NEG | CORNAC_HIP_HOG_ABLATE_MASK;
+    const bool pad_bias = (flags & CORNAC_HIP_HOG_DENSE_BIAS) == 0;  // experiment switch: the dense bias table
+    if (pad_bias) h->Bpad.ensure((size_t)h->total_items * kBiasStride);
+    const unsigned bgrid = (unsigned)((h->total_items + kBlock - 1) / kBlock);
     int64_t left = n_samples;
     while (left > 0) {
         const int64_t n = std::min(left, h->nnz - h->hog_offset);
         HogArgs a;
         fill_hog_args(h, a, n, lr, reg, use_bias, neg_population, flags);
-        const bool pad_bias = (flags & 8) == 0;  // bit3: experiment switch, dense bias table
         a.B = pad_bias ? h->Bpad.p : h->B.p;
         a.bstride = pad_bias ? kBiasStride : 1;
-        const unsigned bgrid = (unsigned)((h->total_items + kBlock - 1) / kBlock);
         if (pad_bias)
             hipLaunchKernelGGL(bias_pad_kernel, dim3(bgrid), dim3(kBlock), 0, h->stream, h->B.p, h->Bpad.p,
                                h->total_items);
@@ -2174,6 +2149,69 @@ static void hogwild_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, flo
         left -= n;
     }
 }
+
+// ---- which form a hogwild call takes ---------------------------------------------------------------------------------
+// The one place that reads the flag word for that.  With form = the form field and low = bits 0..15 (profile builds:
+// bits 0..7, the ablation field is honoured by every form), first row that holds:
+//
+//   low == 0, form AUTO or LDSBIN, ldsbin_can_run                                          -> LdsBin
+//       (a bin plan exists: ldsbin_plan; a passing-bin plan only for launches of >= a quarter epoch; popularity negatives
+//        only over the handle's own interactions, never a caller-supplied population)
+//   low == 0, form STRATA, or AUTO with >= 2^20 items, strata_can_run                      -> Strata
+//       (uniform negatives, user-row ownership, >= 64 items, 8 XCDs)
+//   bits 0..6 == BINNED and nothing else (form field, FUSED_OPT_OUT, ablation field not looked at), plan_binned ok -> Binned
+//       (opt-in: measured slower than the fused atomic kernel at the ML-20M shape)
+//   anything else                                                                          -> Fused
+//
+// So a FORM_STRATA / FORM_LDSBIN word with any low bit set — FUSED_OPT_OUT and the reserved bit 5 included — is not that
+// form, FORM_FUSED | BINNED still runs the binned path, and a BINNED request the plan turns down runs the fused kernel
+// as if the bit were clear.  *bin receives the binned path's plan when that is the answer.
+enum class HogForm { Fused, Binned, Strata, LdsBin };
+static HogForm hog_form(cornac_hip_bpr_t h, int64_t n_samples, int neg_population, int flags, BinPlan *bin = nullptr) {
+    const int form = flags & CORNAC_HIP_HOG_FORM_MASK;
+    int low = flags & 0xffff;  // everything below the form field
+#ifdef CORNAC_PROFILE
+    low &= ~CORNAC_HIP_HOG_ABLATE_MASK;
+#endif
+    if (low == 0) {
+        if ((form == CORNAC_HIP_FORM_AUTO || form == CORNAC_HIP_FORM_LDSBIN) && ldsbin_can_run(h, n_samples, neg_population))
+            return HogForm::LdsBin;
+        if ((form == CORNAC_HIP_FORM_STRATA || (form == CORNAC_HIP_FORM_AUTO && h->n_items >= (int64_t(1) << 20))) &&
+            strata_can_run(h, neg_population))
+            return HogForm::Strata;
+    }
+    if ((flags & 0xff & ~CORNAC_HIP_HOG_FUSED_OPT_OUT) == CORNAC_HIP_HOG_BINNED) {
+        const BinPlan pl = plan_binned(h);
+        if (bin) *bin = pl;
+        if (pl.ok) return HogForm::Binned;
+    }
+    return HogForm::Fused;
+}
+
+static void hogwild_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg, int use_bias,
+                            int neg_population, int flags) {
+    REQUIRE(h->hog_seeded, "hogwild mode needs cornac_hip_bpr_seed_hogwild first");
+    BinPlan bin;
+    switch (hog_form(h, n_samples, neg_population, flags, &bin)) {
+        case HogForm::LdsBin: ldsbin_enqueue(h, n_samples, lr, reg, use_bias, neg_population, flags); break;
+        case HogForm::Strata: strata_enqueue(h, n_samples, lr, reg, use_bias, flags); break;
+        case HogForm::Binned: binned_enqueue(h, bin, n_samples, lr, reg, use_bias, neg_population, flags); break;
+        case HogForm::Fused: fused_enqueue(h, n_samples, lr, reg, use_bias, neg_population, flags); break;
+    }
+}
+
+// The scope of a hogwild entry point: the strata form keeps its packed item records (strata_enqueue) across the calls of
+// an entry point that allows it (`entry_allows`: fit_epochs in hogwild mode; the chunk API once
+// cornac_hip_bpr_chunk_records said so); any other form, like any other entry point (bpr_check), gets the dense tables
+// back first.
+struct PackedRecords {
+    cornac_hip_bpr_t h;
+    PackedRecords(cornac_hip_bpr_t h, bool entry_allows, int64_t n_samples, int neg_population, int flags) : h(h) {
+        h->strata_allow_pack = entry_allows && h->hog_seeded && hog_form(h, n_samples, neg_population, flags) == HogForm::Strata;
+        if (!h->strata_allow_pack) strata_unpack(h);
+    }
+    ~PackedRecords() { h->strata_allow_pack = false; }
+};
 
 static void fetch_counters(cornac_hip_bpr_t h, int64_t *correct, int64_t *skipped) {
     unsigned long long c[4];
@@ -2191,22 +2229,13 @@ extern "C" {
 int cornac_hip_bpr_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, float reg, int use_bias, int neg_population,
                               int mode, int hogwild_flags, int64_t *correct, int64_t *skipped) {
     return guarded([&] {
-        bpr_check_keep_packed(h);
+        bpr_check(h, Records::Keep);
         REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
         REQUIRE(neg_population == CORNAC_HIP_NEG_UNIFORM || neg_population == CORNAC_HIP_NEG_POPULARITY,
                 "unknown neg_population %d", neg_population);
         REQUIRE(mode == CORNAC_HIP_MODE_DETERMINISTIC || mode == CORNAC_HIP_MODE_HOGWILD, "unknown mode %d", mode);
         REQUIRE(!h->f64, "the handle holds float64 tables: use cornac_hip_bpr_fit_epochs_f64 (sequential semantics only)");
-        // the strata form keeps its packed item records from one fit_epochs call to the next; any other form (and any
-        // other entry point: bpr_check) gets the dense tables back first
-        struct AllowPack {
-            cornac_hip_bpr_t h;
-            ~AllowPack() { h->strata_allow_pack = false; }
-        } allow_guard{h};
-        h->strata_allow_pack = mode == CORNAC_HIP_MODE_HOGWILD && h->hog_seeded &&
-                               !hogwild_uses_ldsbin(h, h->nnz, neg_population, hogwild_flags) &&
-                               hogwild_uses_strata(h, h->nnz, neg_population, hogwild_flags);
-        if (!h->strata_allow_pack) strata_unpack(h);
+        const PackedRecords records(h, mode == CORNAC_HIP_MODE_HOGWILD, h->nnz, neg_population, hogwild_flags);
         if (correct) *correct = 0;
         if (skipped) *skipped = 0;
         for (double &t : h->timing) t = 0;
@@ -2231,7 +2260,7 @@ int cornac_hip_bpr_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, float 
 int cornac_hip_bpr_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr, double reg, int use_bias, int neg_population,
                                   int64_t *correct, int64_t *skipped) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->f64, "set float64 tables first (cornac_hip_bpr_set_factors_f64)");
         REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
         REQUIRE(neg_population == CORNAC_HIP_NEG_UNIFORM || neg_population == CORNAC_HIP_NEG_POPULARITY,
@@ -2250,16 +2279,10 @@ int cornac_hip_bpr_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr, d
 int cornac_hip_bpr_hogwild_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg, int use_bias,
                                    int neg_population, int hogwild_flags) {
     return guarded([&] {
-        if (h && h->chunk_records) bpr_check_keep_packed(h); else bpr_check(h);
+        bpr_check(h, Records::Keep);  // (PackedRecords below unpacks unless this chunk may keep them)
         REQUIRE(n_samples >= 0, "n_samples must be >= 0");
         REQUIRE(!h->f64, "the handle holds float64 tables: use cornac_hip_bpr_fit_epochs_f64 (sequential semantics only)");
-        struct AllowPack {
-            cornac_hip_bpr_t h;
-            ~AllowPack() { h->strata_allow_pack = false; }
-        } allow_guard{h};
-        h->strata_allow_pack = h->chunk_records && h->hog_seeded && !hogwild_uses_ldsbin(h, n_samples, neg_population, hogwild_flags) &&
-                               hogwild_uses_strata(h, n_samples, neg_population, hogwild_flags);
-        if (!h->strata_allow_pack) strata_unpack(h);
+        const PackedRecords records(h, h->chunk_records, n_samples, neg_population, hogwild_flags);
         hogwild_enqueue(h, n_samples, lr, reg, use_bias, neg_population, hogwild_flags);
     });
 }
@@ -2284,10 +2307,11 @@ static LdsBinExchange resident_exchange_args(cornac_hip_bpr_t h, int n_exchanges
 
 int cornac_hip_bpr_resident_exchange_bins(cornac_hip_bpr_t h, int neg_population, int hogwild_flags, int *n_bins) {
     return guarded([&] {
-        bpr_check_keep_packed(h);
+        bpr_check(h, Records::Keep);
         REQUIRE(n_bins != nullptr, "n_bins is NULL");
-        *n_bins = (h->hog_seeded && !h->f64 && hogwild_uses_ldsbin(h, h->nnz, neg_population, hogwild_flags) && !ldsbin_plan(h).passing)
-                      ? ldsbin_plan_bins(h) : 0;
+        const LbPlan pl = ldsbin_plan(h);
+        *n_bins = (h->hog_seeded && !h->f64 && !pl.passing && hog_form(h, h->nnz, neg_population, hogwild_flags) == HogForm::LdsBin)
+                      ? pl.bins : 0;
     });
 }
 
@@ -2296,12 +2320,12 @@ int cornac_hip_bpr_epoch_resident_enqueue(cornac_hip_bpr_t h, float lr, float re
                                           int64_t bucket_stride, float *d_keeps, int64_t keep_stride, uint32_t *d_arrive,
                                           const uint32_t *d_landed, uint32_t *d_applied, int *n_arrivals) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->hog_seeded, "hogwild mode needs cornac_hip_bpr_seed_hogwild first");
         REQUIRE(!h->f64, "the handle holds float64 tables");
         REQUIRE(neg_population == CORNAC_HIP_NEG_UNIFORM || neg_population == CORNAC_HIP_NEG_POPULARITY,
                 "unknown neg_population %d", neg_population);
-        REQUIRE(hogwild_uses_ldsbin(h, h->nnz, neg_population, hogwild_flags),
+        REQUIRE(hog_form(h, h->nnz, neg_population, hogwild_flags) == HogForm::LdsBin,
                 "the resident exchange lives in the LDS-bin form, which this shape / these flags do not take "
                 "(cornac_hip_bpr_resident_exchange_bins tells): use cornac_hip_bpr_hogwild_enqueue chunks");
         REQUIRE(!ldsbin_plan(h).passing, "the resident exchange needs resident bins (the item table in <= %d rounds); this table "
@@ -2322,7 +2346,7 @@ int cornac_hip_bpr_epoch_resident_enqueue(cornac_hip_bpr_t h, float lr, float re
 int cornac_hip_bpr_conveyor_setup(cornac_hip_bpr_t h, int n_blocks, const int32_t *rank_item, uint64_t deal_seed,
                                   int release_item_tables, int *n_bins, int *bins_per_block, int *cap) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n_blocks >= 1 && n_blocks <= (1 << 16), "n_blocks out of range");
         REQUIRE(!h->f64, "the handle holds float64 tables");
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -2362,7 +2386,7 @@ int cornac_hip_bpr_conveyor_setup(cornac_hip_bpr_t h, int n_blocks, const int32_
 
 int cornac_hip_bpr_conveyor_layout(cornac_hip_bpr_t h, uint32_t layout_epoch, int32_t *d_slot_item, int32_t *d_item_slot) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->cv_blocks && h->lb_built, "cornac_hip_bpr_conveyor_setup first");
         REQUIRE(d_slot_item || d_item_slot, "NULL device pointers");
         const int64_t total = (int64_t)h->lb_bins * h->lb_cap;
@@ -2378,7 +2402,7 @@ int cornac_hip_bpr_conveyor_enqueue(cornac_hip_bpr_t h, uint32_t epoch, uint32_t
                                     const int32_t *first_block, float *const *d_rows, float lr, float reg, int use_bias,
                                     int neg_population, int hogwild_flags) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->cv_blocks && h->lb_built, "cornac_hip_bpr_conveyor_setup first");
         REQUIRE(h->hog_seeded, "hogwild mode needs cornac_hip_bpr_seed_hogwild first");
         REQUIRE(n_ranges >= 1 && n_ranges <= kLbMaxRanges, "n_ranges must be in [1, %d]", kLbMaxRanges);
@@ -2414,7 +2438,7 @@ int cornac_hip_bpr_resident_flush(cornac_hip_bpr_t h, int n_exchanges, int rule,
                                   int64_t bucket_stride, const float *d_keeps, int64_t keep_stride,
                                   const uint32_t *d_applied, const uint32_t *d_landed) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         // d_landed (may be NULL = all landed): an exchange whose flag is still 0 — the communication stream gave up waiting
         // for its arrivals — is left unapplied
         const LdsBinExchange ex = resident_exchange_args(h, n_exchanges, rule, d_base, const_cast<float *>(d_buckets), bucket_stride,
@@ -2467,14 +2491,14 @@ int cornac_hip_stream_ring_standin(int device, void *hip_stream, const float *d_
 
 int cornac_hip_bpr_chunk_records(cornac_hip_bpr_t h, int enable) {
     return guarded([&] {
-        bpr_check(h);  // (dense tables current: the mode starts and ends with them)
+        bpr_check(h, Records::Unpack);  // (dense tables current: the mode starts and ends with them)
         h->chunk_records = enable != 0;
     });
 }
 
 int cornac_hip_bpr_sync(cornac_hip_bpr_t h, int64_t *correct, int64_t *skipped) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (touches no table: packed strata records stay ...
+        bpr_check(h, Records::Keep);  // (touches no table: packed strata records stay ...
         if (!h->V.owned || !h->B.owned) strata_unpack(h);  // ... unless the dense table is the caller's: it reads it after this call)
         if (correct) *correct = 0;
         if (skipped) *skipped = 0;
@@ -2484,7 +2508,7 @@ int cornac_hip_bpr_sync(cornac_hip_bpr_t h, int64_t *correct, int64_t *skipped) 
 
 int cornac_hip_bpr_debug_draw(cornac_hip_bpr_t h, int stream, uint64_t hi, int64_t n, int64_t *out) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->mt_seeded, "seed the mt19937 streams first");
         REQUIRE(stream == 0 || stream == 1, "stream must be 0 or 1");
         REQUIRE(n >= 0 && out != nullptr, "bad output");
@@ -2503,15 +2527,14 @@ int cornac_hip_bpr_debug_draw(cornac_hip_bpr_t h, int stream, uint64_t hi, int64
 int cornac_hip_bpr_debug_ownership(cornac_hip_bpr_t h, int64_t *n_waves, int64_t *wave_ptr, int32_t *own_u,
                                    int32_t *own_i) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n_waves != nullptr, "n_waves is NULL");
         *n_waves = 0;
         if (!hogwild_uses_ownership(h, 0)) return;
         // the tables of the default throughput path (flags == 0): the strata kernel's grid where that form applies,
         // else the fused kernel's; tables already built for a launch are returned as they are
         if (h->own_waves == 0) {
-            if (!hogwild_uses_ldsbin(h, h->nnz, CORNAC_HIP_NEG_UNIFORM, 0) &&
-                hogwild_uses_strata(h, h->nnz, CORNAC_HIP_NEG_UNIFORM, 0)) {
+            if (hog_form(h, h->nnz, CORNAC_HIP_NEG_UNIFORM, 0) == HogForm::Strata) {
                 strata_prepare(h);
             } else {
                 HogKernel kern = pick_hogwild_kernel<true>(h->k, 0);
@@ -2530,7 +2553,7 @@ int cornac_hip_bpr_debug_ownership(cornac_hip_bpr_t h, int64_t *n_waves, int64_t
 
 int cornac_hip_bpr_kernel_timing(cornac_hip_bpr_t h, int enable, double *total_ms, int64_t *launches) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (touches no table: packed strata records stay)
+        bpr_check(h, Records::Keep);  // (touches no table: packed strata records stay)
         HIP_CHECK(hipStreamSynchronize(h->stream));
         h->ktimer.collect(total_ms, launches);
         h->ktimer.enabled = enable != 0;
@@ -2539,7 +2562,7 @@ int cornac_hip_bpr_kernel_timing(cornac_hip_bpr_t h, int enable, double *total_m
 
 int cornac_hip_bpr_strata_config(cornac_hip_bpr_t h, int hot_permille, int hot_min_mult_x100, int rehash_period) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(hot_permille >= 0 && hot_permille <= 1000, "hot_permille must be in [0, 1000]");
         REQUIRE(hot_min_mult_x100 >= 0, "hot_min_mult_x100 must be >= 0");
         REQUIRE(rehash_period >= 1, "rehash_period must be >= 1");
@@ -2553,7 +2576,7 @@ int cornac_hip_bpr_strata_config(cornac_hip_bpr_t h, int hot_permille, int hot_m
 
 int cornac_hip_bpr_strata_stats(cornac_hip_bpr_t h, int64_t *out4) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (touches no table: packed strata records stay)
+        bpr_check(h, Records::Keep);  // (touches no table: packed strata records stay)
         REQUIRE(out4 != nullptr, "out4 is NULL");
         HIP_CHECK(hipStreamSynchronize(h->stream));
         out4[0] = h->strata_ranked ? (int64_t)h->strata_n_hot : -1;
@@ -2566,9 +2589,9 @@ int cornac_hip_bpr_strata_stats(cornac_hip_bpr_t h, int64_t *out4) {
 int cornac_hip_bpr_debug_strata(cornac_hip_bpr_t h, uint32_t epoch, int64_t *sptr, int32_t *rec_u, int32_t *rec_i,
                                 int32_t *rank_item, uint32_t *key) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->hog_seeded, "seed the hogwild sampler first");
-        REQUIRE(hogwild_uses_strata(h, h->nnz, CORNAC_HIP_NEG_UNIFORM, 2 << 16), "this shape cannot run the strata form");
+        REQUIRE(hog_form(h, h->nnz, CORNAC_HIP_NEG_UNIFORM, CORNAC_HIP_FORM_STRATA) == HogForm::Strata, "this shape cannot run the strata form");
         const int grid = strata_prepare(h);
         const uint32_t kk = strata_key(h->hog_seed, epoch / (uint32_t)std::max(1, h->strata_rehash_period));
         strata_build_buckets(h, grid, kk);
@@ -2584,7 +2607,7 @@ int cornac_hip_bpr_debug_strata(cornac_hip_bpr_t h, uint32_t epoch, int64_t *spt
 
 int cornac_hip_bpr_ldsbin_config(cornac_hip_bpr_t h, int hot_x1000, int min_candidates, int max_rounds) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(hot_x1000 >= 1, "hot_x1000 must be >= 1");
         REQUIRE(min_candidates >= 1, "min_candidates must be >= 1");
         REQUIRE(max_rounds >= 1 && max_rounds <= 1024, "max_rounds must be in [1, 1024]");
@@ -2597,7 +2620,7 @@ int cornac_hip_bpr_ldsbin_config(cornac_hip_bpr_t h, int hot_x1000, int min_cand
 
 int cornac_hip_bpr_ldsbin_pass_config(cornac_hip_bpr_t h, int enable, int waves, int lds_kb, int min_draws_x100) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(waves == 4 || waves == 8 || waves == 16, "waves per workgroup must be 4, 8 or 16");
         REQUIRE(lds_kb >= 16 && lds_kb <= 156, "lds_kb must be in [16, 156]");
         REQUIRE(min_draws_x100 >= 0, "min_draws_x100 must be >= 0");
@@ -2611,7 +2634,7 @@ int cornac_hip_bpr_ldsbin_pass_config(cornac_hip_bpr_t h, int enable, int waves,
 
 int cornac_hip_bpr_ldsbin_deal_config(cornac_hip_bpr_t h, int strata_groups, int hot_cost_x16) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(strata_groups >= 1, "strata_groups must be >= 1");
         REQUIRE(hot_cost_x16 >= 0 && hot_cost_x16 <= 4096, "hot_cost_x16 must be in [0, 4096]");
         h->lb_strata_groups = strata_groups;
@@ -2623,8 +2646,8 @@ int cornac_hip_bpr_ldsbin_deal_config(cornac_hip_bpr_t h, int strata_groups, int
 int cornac_hip_bpr_debug_ldsbin_deal(cornac_hip_bpr_t h, uint64_t seed, uint32_t epoch, int32_t *bin_of_item,
                                      uint32_t *cold_mass, uint32_t *hot_off, int32_t *hot_u, int32_t *hot_i) {
     return guarded([&] {
-        bpr_check(h);
-        const int bins = ldsbin_plan_bins(h);
+        bpr_check(h, Records::Unpack);
+        const int bins = ldsbin_plan(h).bins;
         REQUIRE(bins > 0, "this shape does not use the LDS-bin form");
         ldsbin_build(h);
         const uint32_t key = ldsbin_key(seed, epoch);
@@ -2649,10 +2672,10 @@ int cornac_hip_bpr_debug_ldsbin_deal(cornac_hip_bpr_t h, uint64_t seed, uint32_t
 
 int cornac_hip_bpr_ldsbin_stats(cornac_hip_bpr_t h, int64_t *out6) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(out6 != nullptr, "out8 is NULL");
         out6[6] = h->lb_lock_timeouts;
-        const int bins = ldsbin_plan_bins(h);
+        const int bins = ldsbin_plan(h).bins;
         if (bins > 0) ldsbin_build(h);
         out6[0] = bins;
         out6[1] = bins ? h->lb_cap : 0;

@@ -435,7 +435,7 @@ extern "C" {
 int cornac_hip_bpr_sample_triplets(cornac_hip_bpr_t h, int64_t n_draws, int neg_population, int32_t *d_u,
                                    int32_t *d_i, int32_t *d_j) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->hog_seeded, "sampling needs cornac_hip_bpr_seed_hogwild first");
         REQUIRE(n_draws >= 0, "n_draws < 0");
         REQUIRE(neg_population == CORNAC_HIP_NEG_UNIFORM || neg_population == CORNAC_HIP_NEG_POPULARITY, "unknown neg_population");
@@ -477,7 +477,7 @@ int cornac_hip_bpr_apply_triplets(cornac_hip_bpr_t h, const int32_t *d_u, const 
                                   const int32_t *d_slot_j, int64_t n, float *d_rows, float *d_bias, int bias_stride,
                                   float lr, float reg, int use_bias) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0, "n < 0");
         if (n == 0) return;
         REQUIRE(d_u && d_slot_i && d_slot_j && d_rows && d_bias, "NULL device pointer");
@@ -503,7 +503,7 @@ int cornac_hip_bpr_apply_triplets(cornac_hip_bpr_t h, const int32_t *d_u, const 
 
 int cornac_hip_bpr_staged_slots(cornac_hip_bpr_t h, int64_t n_draws, int64_t *n_slots) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n_slots != nullptr && n_draws >= 0, "bad arguments");
         const int64_t W = staged_waves(h);
         *n_slots = 0;
@@ -518,7 +518,7 @@ int cornac_hip_bpr_staged_slots(cornac_hip_bpr_t h, int64_t n_draws, int64_t *n_
 int cornac_hip_bpr_emit_triplets(cornac_hip_bpr_t h, int64_t n_draws, int neg_population, int32_t *d_u, int32_t *d_i,
                                  int32_t *d_j, int64_t slots_cap, int64_t *n_slots) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->hog_seeded, "sampling needs cornac_hip_bpr_seed_hogwild first");
         REQUIRE(n_draws >= 0 && n_slots != nullptr, "bad arguments");
         REQUIRE(neg_population == CORNAC_HIP_NEG_UNIFORM || neg_population == CORNAC_HIP_NEG_POPULARITY, "unknown neg_population");
@@ -559,7 +559,7 @@ int cornac_hip_bpr_apply_staged(cornac_hip_bpr_t h, const int32_t *d_u, const in
                                 int64_t n_slots, float *d_rows, float *d_bias, int bias_stride, float lr, float reg,
                                 int use_bias) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n_slots >= 0, "n_slots < 0");
         if (n_slots == 0) return;
         REQUIRE(d_u && d_slot_i && d_slot_j && d_rows && d_bias, "NULL device pointer");
@@ -588,7 +588,7 @@ int cornac_hip_bpr_apply_staged(cornac_hip_bpr_t h, const int32_t *d_u, const in
 int cornac_hip_bpr_scatter_diff_rows(cornac_hip_bpr_t h, float *d_table, const int32_t *d_ids, int64_t n, int width,
                                      const float *d_now, const float *d_before, const float *d_scale) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && width > 0, "bad sizes");
         if (n == 0) return;
         REQUIRE(d_table && d_ids && d_now && d_before, "NULL device pointer");
@@ -602,7 +602,7 @@ int cornac_hip_bpr_scatter_diff_rows(cornac_hip_bpr_t h, float *d_table, const i
 int cornac_hip_bpr_shard_mark(cornac_hip_bpr_t h, const int32_t *d_i, const int32_t *d_j, int64_t n, int world,
                               int64_t rows_per_rank, int32_t *d_mark) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && world >= 1 && rows_per_rank >= 1, "bad sizes");
         if (n == 0) return;
         REQUIRE(d_i && d_j && d_mark, "NULL device pointer");
@@ -615,7 +615,7 @@ int cornac_hip_bpr_shard_mark(cornac_hip_bpr_t h, const int32_t *d_i, const int3
 int cornac_hip_bpr_shard_slots(cornac_hip_bpr_t h, const int32_t *d_i, const int32_t *d_j, int64_t n, int world,
                                int64_t rows_per_rank, const int32_t *d_scan, int32_t *d_slot_i, int32_t *d_slot_j) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && world >= 1 && rows_per_rank >= 1, "bad sizes");
         if (n == 0) return;
         REQUIRE(d_i && d_j && d_scan && d_slot_i && d_slot_j, "NULL device pointer");
@@ -629,7 +629,7 @@ int cornac_hip_bpr_shard_slots(cornac_hip_bpr_t h, const int32_t *d_i, const int
 int cornac_hip_bpr_shard_uniq(cornac_hip_bpr_t h, const int32_t *d_mark, const int32_t *d_scan, int64_t n_rows,
                               int64_t rows_per_rank, int32_t *d_uniq_local) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n_rows >= 0 && rows_per_rank >= 1, "bad sizes");
         if (n_rows == 0) return;
         REQUIRE(d_mark && d_scan && d_uniq_local, "NULL device pointer");
@@ -643,7 +643,7 @@ int cornac_hip_bpr_shard_uniq(cornac_hip_bpr_t h, const int32_t *d_mark, const i
 int cornac_hip_bpr_gather_rows(cornac_hip_bpr_t h, const float *d_table, const int32_t *d_ids, int64_t n, int width,
                                float *d_out) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && width > 0, "bad sizes");
         if (n == 0) return;
         REQUIRE(d_table && d_ids && d_out, "NULL device pointer");
@@ -656,7 +656,7 @@ int cornac_hip_bpr_gather_rows(cornac_hip_bpr_t h, const float *d_table, const i
 int cornac_hip_bpr_scatter_add_rows(cornac_hip_bpr_t h, float *d_table, const int32_t *d_ids, int64_t n, int width,
                                     const float *d_delta) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(n >= 0 && width > 0, "bad sizes");
         if (n == 0) return;
         REQUIRE(d_table && d_ids && d_delta, "NULL device pointer");
@@ -682,7 +682,7 @@ static float *table_delta_records(cornac_hip_bpr_t h, const float *d_flat, int64
 int cornac_hip_bpr_table_delta_begin(cornac_hip_bpr_t h, const float *d_flat, const float *d_base, int64_t n_items,
                                      int k, float *d_bucket, float *d_local) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (the pass works on the packed records when they are what the handle trains on)
+        bpr_check(h, Records::Keep);  // (the pass works on the packed records when they are what the handle trains on)
         REQUIRE(n_items > 0 && k > 0 && d_flat && d_base && d_bucket && d_local, "bad arguments");
         float *rec = table_delta_records(h, d_flat, n_items, k);
         launch_table_delta(0, 0, h->stream, const_cast<float *>(d_flat), const_cast<float *>(d_base), nullptr, nullptr, n_items,
@@ -694,7 +694,7 @@ int cornac_hip_bpr_table_delta_begin(cornac_hip_bpr_t h, const float *d_flat, co
 int cornac_hip_bpr_table_delta_finish(cornac_hip_bpr_t h, float *d_flat, float *d_base, const float *d_bucket,
                                       const float *d_local, int64_t n_items, int k) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (the pass works on the packed records when they are what the handle trains on)
+        bpr_check(h, Records::Keep);  // (the pass works on the packed records when they are what the handle trains on)
         REQUIRE(n_items > 0 && k > 0 && d_flat && d_base && d_bucket && d_local, "bad arguments");
         float *rec = table_delta_records(h, d_flat, n_items, k);
         launch_table_delta(1, 0, h->stream, d_flat, d_base, d_bucket, d_local, n_items, k, nullptr, nullptr, rec, h->vb_pitch,
@@ -706,7 +706,7 @@ int cornac_hip_bpr_table_delta_finish(cornac_hip_bpr_t h, float *d_flat, float *
 int cornac_hip_bpr_table_delta_step(cornac_hip_bpr_t h, float *d_flat, float *d_base, const float *d_bucket_prev,
                                     const float *d_local_prev, int64_t n_items, int k, float *d_bucket, float *d_local) {
     return guarded([&] {
-        bpr_check_keep_packed(h);  // (the pass works on the packed records when they are what the handle trains on)
+        bpr_check(h, Records::Keep);  // (the pass works on the packed records when they are what the handle trains on)
         REQUIRE(n_items > 0 && k > 0 && d_flat && d_base && d_bucket_prev && d_local_prev && d_bucket && d_local,
                 "bad arguments");
         float *rec = table_delta_records(h, d_flat, n_items, k);
@@ -721,7 +721,7 @@ int cornac_hip_bpr_table_delta_step(cornac_hip_bpr_t h, float *d_flat, float *d_
 int cornac_hip_bpr_table_delta(cornac_hip_bpr_t h, int op, int rule, float *d_flat, float *d_base, const float *d_bucket_prev,
                                const float *d_local_prev, int64_t n_items, int k, float *d_bucket, float *d_local) {
     return guarded([&] {
-        bpr_check_keep_packed(h);
+        bpr_check(h, Records::Keep);
         REQUIRE(op >= 0 && op <= 2, "op must be 0 (begin), 1 (finish) or 2 (step)");
         REQUIRE(rule == 0 || rule == 1, "rule must be 0 (sqrt) or 1 (align)");
         REQUIRE(n_items > 0 && k > 0 && d_flat && d_base, "bad arguments");

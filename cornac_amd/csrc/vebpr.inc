@@ -426,7 +426,7 @@ extern "C" {
 int cornac_hip_bpr_set_views(cornac_hip_bpr_t h, const int32_t *view_indptr, const int32_t *view_indices,
                              int64_t nnz_view) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(view_indptr != nullptr && nnz_view >= 0, "bad view matrix");
         REQUIRE(view_indptr[0] == 0 && (int64_t)view_indptr[h->n_users] == nnz_view, "view indptr does not match nnz");
         for (int64_t u = 0; u < h->n_users; ++u)
@@ -446,7 +446,7 @@ int cornac_hip_bpr_set_views(cornac_hip_bpr_t h, const int32_t *view_indptr, con
 
 int cornac_hip_bpr_seed_view_stream(cornac_hip_bpr_t h, uint32_t mt_seed_view) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->mt_seeded, "seed the positive/negative streams first (cornac_hip_bpr_seed_mt19937)");
         std::vector<uint32_t> st(MT_N);
         mt_init_genrand(mt_seed_view, st.data());
@@ -461,7 +461,7 @@ int cornac_hip_bpr_seed_view_stream(cornac_hip_bpr_t h, uint32_t mt_seed_view) {
 int cornac_hip_vebpr_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, float reg, float alpha, int mode,
                                 int64_t *correct, int64_t *skipped) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(!h->f64, "the handle holds float64 tables (VEBPR trains float32 tables here)");
         REQUIRE(h->has_views, "cornac_hip_bpr_set_views has not been called");
         REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
@@ -485,7 +485,7 @@ int cornac_hip_vebpr_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, floa
 int cornac_hip_vebpr_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr, double reg, double alpha, int64_t *correct,
                                     int64_t *skipped) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(h->f64, "set float64 tables first (cornac_hip_bpr_set_factors_f64; the bias table is not used)");
         REQUIRE(h->has_views, "cornac_hip_bpr_set_views has not been called");
         REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
@@ -502,7 +502,7 @@ int cornac_hip_vebpr_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr,
 
 int cornac_hip_vebpr_hogwild_form(cornac_hip_bpr_t h, int *owned) {
     return guarded([&] {
-        bpr_check(h);
+        bpr_check(h, Records::Unpack);
         REQUIRE(owned != nullptr, "owned is NULL");
         *owned = h->vebpr_owned ? 1 : 0;
     });

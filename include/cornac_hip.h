@@ -122,25 +122,42 @@ int cornac_hip_bpr_seed_hogwild(cornac_hip_bpr_t h, uint64_t seed);
  * caller's population the popularity draw runs in the fused kernel (the LDS-bin form weights by the handle's own CSC). */
 int cornac_hip_bpr_set_negative_population(cornac_hip_bpr_t h, const int32_t *items, int64_t n);
 
+/* The bits of hogwild_flags (explained at cornac_hip_bpr_fit_epochs below). */
+#define CORNAC_HIP_HOG_PLAIN_STORES 1    /* bit0: plain (racy, non-atomic, XCD-incoherent) row stores, not fp32 atomics */
+#define CORNAC_HIP_HOG_VEC4_LAYOUT 2     /* bit1: the float4-per-lane row layout                                        */
+#define CORNAC_HIP_HOG_NO_OWNERSHIP 4    /* bit2: no user-row ownership (all rows atomic)                               */
+#define CORNAC_HIP_HOG_DENSE_BIAS 8      /* bit3: the dense bias table, not one bias per 128-byte line                  */
+/* bit4: (k in 33..64) the four sampling lanes 4g..4g+3 share one negative item and its row gets ONE combined atomic
+ * update — a different joint distribution of the draws than the reference's, kept as a measured experiment */
+#define CORNAC_HIP_HOG_SHARE_NEG 16
+/* bit5 (32): reserved.  No kernel reads it; like every set bit below the form field it keeps the call out of the
+ * LDS-bin, XCD-strata and binned forms, so a word that carries it runs the fused kernel as if it did not. */
+/* bit6: the segmented ("binned") item-update path (k in 33..256); taken only when it is the one bit set among bits 0..6 */
+#define CORNAC_HIP_HOG_BINNED 64
+#define CORNAC_HIP_HOG_FUSED_OPT_OUT 128 /* bit7: opts out of the LDS-bin / XCD-strata forms, nothing else              */
+#define CORNAC_HIP_HOG_ABLATE_MASK 0xff00 /* bits 8..15: ablation switches of the SGD kernels (profile builds only)     */
+#define CORNAC_HIP_HOG_ABLATE_SHIFT 8
+#define CORNAC_HIP_HOG_FORM_MASK 0xf0000  /* bits 16..19: the form field                                                */
+#define CORNAC_HIP_HOG_FORM_SHIFT 16
+#define CORNAC_HIP_FORM_AUTO (0 << CORNAC_HIP_HOG_FORM_SHIFT)
+#define CORNAC_HIP_FORM_FUSED (1 << CORNAC_HIP_HOG_FORM_SHIFT)
+#define CORNAC_HIP_FORM_STRATA (2 << CORNAC_HIP_HOG_FORM_SHIFT)
+#define CORNAC_HIP_FORM_LDSBIN (3 << CORNAC_HIP_HOG_FORM_SHIFT)
+
 /* Run n_epochs epochs of nnz samples each.  correct/skipped accumulate the
  * reference's per-epoch counters over the epochs run (either may be NULL).
- * hogwild_flags (0 = default).  Bits 16..19 select the form of a hogwild call:
- * 0 = automatic, 1 = the fused kernel (every item-row update a device-scope fp32 atomic; also bit7), 2 = XCD strata
- * (csrc/bpr_strata.inc: 8 launches per epoch, an item row is touched by one XCD per launch and updated by plain
- * read-modify-write like the reference's threads), 3 = LDS-resident item bins (csrc/bpr_ldsbin.inc: the item rows
- * of a bin live in one CU's LDS for the epoch, exact updates, user rows by atomics).  Automatic = LDS bins when the
- * item table fits the LDS in at most max_rounds rounds with at least min_candidates items per bin, else XCD strata
- * for item tables of >= 2^20 rows, else the fused kernel.  A chunk of an epoch (hogwild_enqueue) runs in the same form:
- * an LDS-bin launch takes its share of every bin's draws, an XCD-strata chunk runs the partition phases that begin
- * inside it.  Popularity negatives (WBPR) have the LDS-bin form too — the negative is the item of a second interaction
- * drawn from the bin's own draw space, hot items dealt to every bin — but not the XCD-strata one; every experiment
- * switch below runs the fused kernel.
- * Experiment switches of the fused kernel: bit0 = plain (racy,
- * non-atomic, XCD-incoherent) row stores instead of fp32 atomics; bit1 = the
- * float4-per-lane row layout; bit2 = no user-row ownership (all rows atomic);
- * bit4 = (k in 33..64) the four sampling lanes 4g..4g+3 share one negative item and its row gets ONE combined atomic
- * update — a different joint distribution of the draws than the reference's, kept as a measured experiment;
- * bit6 = the segmented ("binned") item-update path. */
+ * hogwild_flags (0 = default) is the word of CORNAC_HIP_HOG_* bits above.  Its form field selects the form of a
+ * hogwild call: CORNAC_HIP_FORM_AUTO, CORNAC_HIP_FORM_FUSED (every item-row update a device-scope fp32 atomic; also
+ * CORNAC_HIP_HOG_FUSED_OPT_OUT), CORNAC_HIP_FORM_STRATA (csrc/bpr_strata.inc: 8 launches per epoch, an item row is
+ * touched by one XCD per launch and updated by plain read-modify-write like the reference's threads),
+ * CORNAC_HIP_FORM_LDSBIN (csrc/bpr_ldsbin.inc: the item rows of a bin live in one CU's LDS for the epoch, exact
+ * updates, user rows by atomics).  Automatic = LDS bins when the item table fits the LDS in at most max_rounds rounds
+ * with at least min_candidates items per bin, else XCD strata for item tables of >= 2^20 rows, else the fused kernel
+ * (the whole decision: the table over hog_form in csrc/bpr.hip).  A chunk of an epoch (hogwild_enqueue) runs in the
+ * same form: an LDS-bin launch takes its share of every bin's draws, an XCD-strata chunk runs the partition phases that
+ * begin inside it.  Popularity negatives (WBPR) have the LDS-bin form too — the negative is the item of a second
+ * interaction drawn from the bin's own draw space, hot items dealt to every bin — but not the XCD-strata one; every
+ * switch (any of bits 0..15) runs the fused kernel, or the binned path where CORNAC_HIP_HOG_BINNED says so. */
 int cornac_hip_bpr_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, float reg, int use_bias, int neg_population,
                               int mode, int hogwild_flags, int64_t *correct, int64_t *skipped);
 /* Same, but only enqueues `n_samples` hogwild samples (sample counter and

@@ -238,7 +238,7 @@ def test_owned_sampler_and_ownership_tables(oracle):
     seed = 0x1234ABCD5678
     tr.seed_hogwild(seed)
     # bit 7 = the fused kernel whatever the shape (the LDS-bin and XCD-strata samplers have their own tests below)
-    c, s = tr.fit_epochs(2, 0.0, 0.0, True, _lib.NEG_UNIFORM, _lib.MODE_HOGWILD, flags=128)
+    c, s = tr.fit_epochs(2, 0.0, 0.0, True, _lib.NEG_UNIFORM, _lib.MODE_HOGWILD, flags=_lib.HOG_FUSED_OPT_OUT)
     own = tr.debug_ownership()  # the tables the two epochs used
     assert own is not None, "expected the ownership kernel for k=64, nnz=700k"
     wave_ptr, own_u, own_i = own
@@ -777,7 +777,7 @@ def test_owned_kernel_user_rows_are_exact():
     U0 = rs.normal(0, 0.1, (n_users, 64)).astype(np.float32)
     V0 = rs.normal(0, 0.1, (n_items, 64)).astype(np.float32)
     res = []
-    for flags in (128, 4, _lib.FORM_STRATA):  # ownership (fused kernel) vs all-atomic vs the XCD-strata form (same ownership of U rows)
+    for flags in (_lib.HOG_FUSED_OPT_OUT, _lib.HOG_NO_OWNERSHIP, _lib.FORM_STRATA):  # ownership (fused kernel) vs all-atomic vs the XCD-strata form (same ownership of U rows)
         tr = _lib.BprTrainer(indptr, indices, n_users, n_items, n_users, n_items, 64)
         tr.set_factors(U0, V0, np.zeros(n_items, np.float32))
         tr.seed_hogwild(77)
@@ -1014,7 +1014,7 @@ def test_sharded_trainer_single_rank_stream_ordering():
 
 
 def test_binned_item_updates_learn_like_the_fused_atomic_kernel():
-    """hogwild_flags bit 6 (opt-in experiment): the item-side updates go through message segments +
+    """hogwild_flags bit 6, HOG_BINNED (opt-in experiment): the item-side updates go through message segments +
     LDS-resident item buckets with the own-drift correction (bpr_binned.inc) instead of the fused kernel's device-scope
     atomics.  Different wave count, hence different sample streams (skip counts are compared statistically), same
     optimisation problem: training must stay close to the fused kernel."""
@@ -1027,13 +1027,13 @@ def test_binned_item_updates_learn_like_the_fused_atomic_kernel():
     U = ((rs.uniform(0, 1, (n_users, k)) - 0.5) / k).astype(np.float32)
     V = ((rs.uniform(0, 1, (n_items, k)) - 0.5) / k).astype(np.float32)
     out = {}
-    for flags in (64, 128):
+    for flags in (_lib.HOG_BINNED, _lib.HOG_FUSED_OPT_OUT):
         tr = _lib.BprTrainer(indptr, indices, n_users, n_items, n_users, n_items, k)
         tr.set_factors(U, V, np.zeros(n_items, np.float32))
         tr.seed_hogwild(9)
         tr.fit_epochs(6, 0.05, 0.0, True, _lib.NEG_UNIFORM, _lib.MODE_HOGWILD, flags=flags)
         c, s = tr.fit_epochs(1, 0.05, 0.0, True, _lib.NEG_UNIFORM, _lib.MODE_HOGWILD, flags=flags)
-        out[flags & 64] = (c / (len(indices) - s), s, tr.get_factors())
+        out[flags & _lib.HOG_BINNED] = (c / (len(indices) - s), s, tr.get_factors())
         tr.close()
     assert abs(out[64][1] - out[0][1]) < 0.05 * out[0][1] + 50
     assert abs(out[64][0] - out[0][0]) < 0.01, (out[64][0], out[0][0])

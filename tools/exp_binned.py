@@ -32,12 +32,12 @@ def probe(U, V, B):
 
 
 def parse(spec):
-    flags, env = 64, {}
+    flags, env = _lib.HOG_BINNED, {}
     for tok in spec.split("-"):
         if tok == "fused":
-            flags &= ~64
+            flags &= ~_lib.HOG_BINNED
         elif tok == "share":      # fused kernel with negatives shared by groups of 4 sampling lanes (hogwild_flags bit 4)
-            flags = (flags & ~64) | 16
+            flags = (flags & ~_lib.HOG_BINNED) | _lib.HOG_SHARE_NEG
         elif tok.startswith("wg"):
             env["CORNAC_HIP_BIN_WG_PER_CU"] = tok[2:]
         elif tok.startswith("c"):
@@ -49,7 +49,7 @@ def parse(spec):
         elif tok.startswith("ub"):
             env["CORNAC_HIP_BIN_UNRB"] = tok[2:]
         elif tok.startswith("abl"):
-            flags |= int(tok[3:]) << 8
+            flags |= int(tok[3:]) << _lib.HOG_ABLATE_SHIFT
         else:
             raise SystemExit("bad arm token %r" % tok)
     return flags, env

@@ -23,7 +23,7 @@ for spec in (sys.argv[1:] or ["strata", "waves=8,kb=78"]):
     else:
         tr.ldsbin_pass_config(True, int(cfg.get("waves", 8)), int(cfg.get("kb", 78)))
         os.environ["CORNAC_HIP_LDSBIN_UNR"] = cfg.get("unr", "0")
-        flags = int(cfg.get("abl", 0)) << 8
+        flags = int(cfg.get("abl", 0)) << _lib.HOG_ABLATE_SHIFT
     tr.set_factors(U, V, B)
     tr.seed_hogwild(7)
     t0 = time.time()

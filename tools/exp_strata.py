@@ -61,7 +61,7 @@ def parse(spec):
         elif tok.startswith("hc"):
             cfg["hot_cost_x16"] = int(tok[2:])
         elif tok.startswith("abl"):
-            flags |= int(tok[3:]) << 8
+            flags |= int(tok[3:]) << _lib.HOG_ABLATE_SHIFT
         elif tok.startswith("h"):
             cfg["hot_permille"] = int(tok[1:])
         elif tok.startswith("m"):
@@ -125,7 +125,7 @@ for name in args.arms.split(","):
     dt = time.perf_counter() - t0
     kms, launches = tr.kernel_timing(False)
     st = tr.strata_stats()
-    lb = tr.ldsbin_stats() if (flags >> 16) in (0, 3) else None
+    lb = tr.ldsbin_stats() if (flags & _lib.HOG_FORM_MASK) in (_lib.FORM_AUTO, _lib.FORM_LDSBIN) else None
     if lb and lb["bins"]:
         _, cold, off, _, _ = tr.debug_ldsbin_deal(0xC0FFEE, 3)
         tot = cold.astype(np.int64) + np.diff(off.astype(np.int64))

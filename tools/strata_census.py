@@ -28,7 +28,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "big":
 else:
     n_users, n_items, indptr, indices = bench.load_dataset("ml20m", 0, os.environ.get("TMPDIR", "/tmp"))
     k = 64
-flags = 16 << 8
+flags = 16 << _lib.HOG_ABLATE_SHIFT
 
 
 def run(cfg, variant):
