@@ -989,7 +989,8 @@ class WmfTrainer:
         return U, V
 
     def fit_batches(self, batches, lambda_u, lambda_v, a, b, lr):
-        """batches: sequence of item-id arrays (1..128 distinct ids each); returns the per-step losses"""
+        """batches: sequence of item-id arrays (1..128 distinct ids each; a repeated id is rejected, HipError, with the
+        state untouched); returns the per-step losses"""
         batches = [np.asarray(x, np.int32).ravel() for x in batches]
         if not batches:
             return np.zeros(0)

@@ -962,6 +962,7 @@ int cornac_hip_wmf_fit_batches(cornac_hip_wmf_t h, const int32_t *item_ids, cons
         REQUIRE(n_batches >= 0, "n_batches < 0");
         if (n_batches == 0) return;
         REQUIRE(item_ids && batch_ptr, "batch arrays are NULL");
+        std::vector<int32_t> seen;
         for (int64_t bi = 0; bi < n_batches; ++bi) {
             const int64_t B = batch_ptr[bi + 1] - batch_ptr[bi];
             REQUIRE(B > 0 && B <= kMaxBatch, "batch %lld has %lld items; 1..%d supported", (long long)bi, (long long)B, kMaxBatch);
@@ -969,7 +970,16 @@ int cornac_hip_wmf_fit_batches(cornac_hip_wmf_t h, const int32_t *item_ids, cons
                 const int32_t it = item_ids[batch_ptr[bi] + c];
                 REQUIRE(it >= 0 && it < h->n_items, "item id %d out of range", it);
             }
+            // an item twice in one batch: only the column its tag names would be consumed and re-zeroed by wmf_adam_v_kernel, the
+            // other one's dV would leak into the next step (the reference's item_iter never yields one)
+            seen.assign(item_ids + batch_ptr[bi], item_ids + batch_ptr[bi + 1]);
+            std::sort(seen.begin(), seen.end());
+            const auto dup = std::adjacent_find(seen.begin(), seen.end());
+            REQUIRE(dup == seen.end(), "batch %lld holds item id %d more than once", (long long)bi, dup == seen.end() ? -1 : *dup);
         }
+        // slot_tag keeps (step << 7 | column) in 32 bits: beyond 2^25 - 1 steps the tag's step would wrap and no row would match
+        REQUIRE(h->step + n_batches < ((int64_t)1 << 25), "the handle has taken %lld steps; %lld more would pass the 2^25 - 1 its batch "
+                "tags can hold (set_factors restarts the count)", (long long)h->step, (long long)n_batches);
         const double beta1 = 0.9, beta2 = 0.999;
         hipStream_t s = h->stream;
         const int ld = h->ld, k = h->k;

@@ -513,7 +513,9 @@ void cornac_hip_wmf_destroy(cornac_hip_wmf_t h);
 int cornac_hip_wmf_set_factors(cornac_hip_wmf_t h, const float *U, const float *V);
 int cornac_hip_wmf_get_factors(cornac_hip_wmf_t h, float *U, float *V);
 /* one Adam step per batch b = item_ids[batch_ptr[b] .. batch_ptr[b+1]) (1..128 distinct items), in order;
- * loss_out[b] (may be NULL) = that step's loss value (`_loss`, recom_wmf.py:195) */
+ * loss_out[b] (may be NULL) = that step's loss value (`_loss`, recom_wmf.py:195).  The whole call is checked before
+ * anything is enqueued: an id out of range, an item twice in one batch, a batch of 0 or more than 128 items, or a step
+ * count that would reach 2^25 since the last set_factors fails with CORNAC_HIP_ERR_INVALID and changes nothing */
 int cornac_hip_wmf_fit_batches(cornac_hip_wmf_t h, const int32_t *item_ids, const int64_t *batch_ptr,
                                int64_t n_batches, float lambda_u, float lambda_v, float a, float b,
                                float learning_rate, double *loss_out);
