@@ -61,6 +61,7 @@ SYMBOLS = [
     "cornac_hip_mf_sync", "cornac_hip_mf_fit_sgd", "cornac_hip_mf_last_timing",
     "cornac_hip_mf_hogwild_form", "cornac_hip_mf_hogwild_stats",
     "cornac_hip_mf_fit_minibatch", "cornac_hip_mf_fit_minibatch_dropout", "cornac_hip_mf_reset_optimizer",
+    "cornac_hip_mf_pmf_set_factors", "cornac_hip_mf_pmf_get_factors", "cornac_hip_mf_pmf_fit", "cornac_hip_mf_pmf_form",
     "cornac_hip_scorer_create", "cornac_hip_scorer_destroy", "cornac_hip_scorer_set", "cornac_hip_score_user",
     "cornac_hip_scorer_set_f64", "cornac_hip_score_user_f64",
     "cornac_hip_score_block", "cornac_hip_rank_topk", "cornac_hip_rank_topk_device", "cornac_hip_score_pairs",
@@ -221,6 +222,10 @@ def lib():
         L.cornac_hip_mf_fit_minibatch_dropout.argtypes = [_vp, _i64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float,
                                                           C.c_float, C.c_int, _vp, _vp, C.c_float, C.POINTER(C.c_double)]
         L.cornac_hip_mf_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_mf_pmf_set_factors.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_mf_pmf_get_factors.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_mf_pmf_fit.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _vp]
+        L.cornac_hip_mf_pmf_form.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cornac_hip_wmf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, C.c_int, _i64, _i32, _f32,
                                             C.c_int64]
         L.cornac_hip_wmf_destroy.argtypes = [_vp]
@@ -748,6 +753,36 @@ class MfTrainer:
 
     def reset_optimizer(self):
         check(lib().cornac_hip_mf_reset_optimizer(self.h))
+
+    # ---- PMF on the same handle (float64 tables and RMSProp caches beside the float32 MF state) ------------------
+    PMF_VARIANTS = {"linear": 0, "non_linear": 1}
+
+    def pmf_set_factors(self, U, V):
+        """float64 U [n_users, k], V [n_items, k]; zeroes the RMSProp caches"""
+        nu, ni, k = self.shape
+        U, V = np.ascontiguousarray(U, np.float64), np.ascontiguousarray(V, np.float64)
+        if U.shape != (nu, k) or V.shape != (ni, k):
+            raise ValueError("PMF tables must be %r and %r, got %r and %r" % ((nu, k), (ni, k), U.shape, V.shape))
+        check(lib().cornac_hip_mf_pmf_set_factors(self.h, U.ctypes.data, V.ctypes.data))
+
+    def pmf_get_factors(self):
+        nu, ni, k = self.shape
+        U, V = np.empty((nu, k), np.float64), np.empty((ni, k), np.float64)
+        check(lib().cornac_hip_mf_pmf_get_factors(self.h, U.ctypes.data, V.ctypes.data))
+        return U, V
+
+    def pmf_fit(self, n_epochs, lr, reg, gamma, variant):
+        """n_epochs sequential epochs (variant: "linear" / "non_linear" or the ABI's code); the loss of each"""
+        loss = np.zeros(max(int(n_epochs), 1), np.float64)
+        check(lib().cornac_hip_mf_pmf_fit(self.h, int(n_epochs), lr, reg, gamma, self.PMF_VARIANTS.get(variant, variant),
+                                          loss.ctypes.data))
+        return loss[:max(int(n_epochs), 0)]
+
+    def pmf_form(self):
+        """(form, group) of the last PMF epoch: 1 dataflow launch / 2 level schedule / 0 none yet, ratings per wave pass"""
+        form, group = C.c_int(), C.c_int()
+        check(lib().cornac_hip_mf_pmf_form(self.h, C.byref(form), C.byref(group)))
+        return form.value, group.value
 
     def kernel_timing(self, enable=True):
         ms, n = C.c_double(), C.c_int64()

@@ -483,6 +483,10 @@ struct cornac_hip_mf {
     int64_t opt_step = 0;
     int opt_kind = -1;
     bool enqueue_open = false;  // epoch_enqueue has accumulated into loss[0] since the last cornac_hip_mf_sync
+    // PMF (pmf.inc): float64 factors and RMSProp caches beside the float32 MF state; the dataflow plan above is shared
+    DevBuf<double> pmf_U, pmf_V, pmf_cu, pmf_cv, pmf_loss;
+    bool pmf_set = false, pmf_chain_refused = false;
+    int pmf_form = 0, pmf_group = 0;  // last epoch: 1 dataflow launch / 2 level schedule, ratings per wave pass
 };
 
 #include "mf_blocks.inc"
@@ -580,7 +584,8 @@ static MfChainKernel pick_chain_kernel(int k, bool own_user) {
 
 static bool mf_uses_chain(cornac_hip_mf_t h) { return h->k <= 256 && h->nnz >= 4096; }
 
-static void mf_build_chain(cornac_hip_mf_t h) {
+// per_cu_cap: what another kernel that runs the same plan (PMF's, pmf.inc: more registers) admits per CU
+static void mf_build_chain(cornac_hip_mf_t h, int per_cu_cap = 8) {
     if (h->chain_built) return;
     Timer t;
     const int64_t n = h->nnz, ni = h->n_items, nu = h->n_users;
@@ -605,7 +610,7 @@ static void mf_build_chain(cornac_hip_mf_t h) {
     // progress needs the wave that owns the globally first unfinished rating to be running: HALF of what the occupancy
     // query admits keeps every block of the grid resident even where the hardware admits one block per CU fewer than
     // the API says (kernels with more than 80 SGPRs, MI355X_MICROARCH.md, residency)
-    h->chain_grid = device_info(h->device).cus * std::max(1, std::min(per_cu, 8) / 2);
+    h->chain_grid = device_info(h->device).cus * std::max(1, std::min(per_cu, std::min(per_cu_cap, 8)) / 2);
     const int64_t W = (int64_t)h->chain_grid * kWavesPerBlock;
     // owned rows -> waves, heaviest first onto the least loaded wave
     const std::vector<int64_t> &cnt = own_user ? cnt_u : cnt_i;
@@ -1492,3 +1497,4 @@ int cornac_hip_mf_last_timing(cornac_hip_mf_t h, double *ms4) {
 }
 
 #include "mf_minibatch.inc"
+#include "pmf.inc"

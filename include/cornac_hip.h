@@ -446,6 +446,27 @@ int cornac_hip_mf_sync(cornac_hip_mf_t h, double *sq_err_sum);
 int cornac_hip_mf_kernel_timing(cornac_hip_mf_t h, int enable, double *total_ms, int64_t *launches);
 int cornac_hip_mf_last_timing(cornac_hip_mf_t h, double *ms4);
 
+/* PMF on the same handle: the reference's sequential per-rating SGD with an RMSProp cache, in float64.
+ * Replaces: pmf.pmf_linear / pmf.pmf_non_linear(uid, iid, rat, n_users, n_items, n_ratings, k, n_epochs, lambda_reg,
+ *           learning_rate, gamma, init_params, verbose, seed)
+ *           cornac/models/pmf/cython/pmf.pyx:55-111 and :115-173 (called from PMF.fit,
+ *           cornac/models/pmf/recom_pmf.py:143-176); the handle's `val` are the ratings as the reference passes them
+ *           (float32, rescaled to [0, 1] by the caller for the non-linear variant).
+ * Ratings run in the stored order, as on the reference's single thread: one persistent dataflow launch per epoch (k <= 256
+ * and nnz >= 4096; for k <= 32 several ready ratings per wave pass, in lane groups of pow2 >= k lanes), else one launch per
+ * level of the row-conflict schedule.  U and V come out bit-identical to the sequential loop's; the loss is summed in
+ * another order.  The float32 MF state of the handle is untouched. */
+#define CORNAC_HIP_PMF_LINEAR 0
+#define CORNAC_HIP_PMF_NON_LINEAR 1
+/* float64 U [n_users,k], V [n_items,k]; zeroes the RMSProp caches (the reference allocates them per fit call) */
+int cornac_hip_mf_pmf_set_factors(cornac_hip_mf_t h, const double *U, const double *V);
+int cornac_hip_mf_pmf_get_factors(cornac_hip_mf_t h, double *U, double *V);
+/* n_epochs sequential epochs over the stored order; caches persist across calls until set_factors;
+ * loss_per_epoch [n_epochs] may be NULL; lr / reg / gamma are the reference's float arguments */
+int cornac_hip_mf_pmf_fit(cornac_hip_mf_t h, int n_epochs, float lr, float reg, float gamma, int variant, double *loss_per_epoch);
+/* 1 = dataflow launch, 2 = level schedule, 0 = none yet; *group = ratings per wave pass of the last epoch */
+int cornac_hip_mf_pmf_form(cornac_hip_mf_t h, int *form, int *group);
+
 /* Minibatch path with dense optimisers on the same handle.
  * Replaces: backend_pt.learn(model, train_set, n_epochs, batch_size, learning_rate, reg, optimizer)
  *           cornac/models/mf/backend_pt.py:67-106 and the forward of backend_pt.MF (:56-65), selected by
