@@ -772,14 +772,21 @@ int64_t oracle_ldsbin_epoch_skips(uint64_t seed, uint32_t epoch, uint32_t key, u
                                            0u, n_bins);
 }
 
-/* the same for the bins [b_lo, b_hi) only (a conveyor block's launch; a sample of the bins at sizes where the whole epoch
- * would take minutes on one core) */
-int64_t oracle_ldsbin_epoch_skips_range(uint64_t seed, uint32_t epoch, uint32_t key, uint32_t n_bins, uint32_t n_items,
-                                        uint32_t n_hot, uint32_t n_strata, uint32_t hot_cost_x16, const int32_t *rank_item,
-                                        const int32_t *cptr, const int32_t *cusers,
-                                        const int32_t *hot_u, const int32_t *hot_i, uint32_t n_hot_inter, const int32_t *indptr,
-                                        const int32_t *indices, int64_t *n_draws_out, int64_t *pos_count, int64_t *neg_count,
-                                        int neg_pop, uint32_t b_lo, uint32_t b_hi) {
+/* The one restatement of the sampler's loop.  Bins [b_lo, b_hi) (a conveyor block's launch; a sample of the bins at sizes
+ * where the whole epoch would take minutes on one core); of every bin the draws a launch covering [s_begin, s_begin + n) / nnz
+ * of the epoch makes (csrc/bpr_ldsbin.inc ldsbin_launch_range; nnz = 0: all of them).  Returns the skipped draws of that range;
+ * *n_draws_out = the bins' draws of the WHOLE epoch.  pos_count / neg_count: touches per item of the non-skipped draws.
+ * out_u / out_i / out_j / out_bin / out_hot (each may be NULL, room for out_cap entries): the non-skipped triplets in (bin, draw)
+ * order, the bin that drew each, and whether its positive came from the hot list; *n_out = their number, which may exceed
+ * out_cap (then only the first out_cap were written). */
+int64_t oracle_ldsbin_draws(uint64_t seed, uint32_t epoch, uint32_t key, uint32_t n_bins, uint32_t n_items,
+                            uint32_t n_hot, uint32_t n_strata, uint32_t hot_cost_x16, const int32_t *rank_item,
+                            const int32_t *cptr, const int32_t *cusers,
+                            const int32_t *hot_u, const int32_t *hot_i, uint32_t n_hot_inter, const int32_t *indptr,
+                            const int32_t *indices, int64_t *n_draws_out, int64_t *pos_count, int64_t *neg_count,
+                            int neg_pop, uint32_t b_lo, uint32_t b_hi, uint64_t s_begin, uint64_t n, uint64_t nnz,
+                            int32_t *out_u, int32_t *out_i, int32_t *out_j, int32_t *out_bin, uint8_t *out_hot,
+                            int64_t out_cap, int64_t *n_out) {
     const uint32_t n_groups = (n_items + n_bins - 1) / n_bins;
     uint32_t *cold_all = (uint32_t *)malloc(sizeof(uint32_t) * n_bins);
     uint32_t *hot_off = (uint32_t *)malloc(sizeof(uint32_t) * (n_bins + 1));
@@ -789,7 +796,7 @@ int64_t oracle_ldsbin_epoch_skips_range(uint64_t seed, uint32_t epoch, uint32_t 
     int32_t *cp = (int32_t *)malloc(sizeof(int32_t) * n_groups);
     uint32_t *cum = (uint32_t *)malloc(sizeof(uint32_t) * (n_groups + 1));
     uint8_t *hot = (uint8_t *)malloc(n_groups);
-    int64_t skipped = 0, total = 0;
+    int64_t skipped = 0, total = 0, kept = 0;
     for (uint32_t b = b_lo; b < b_hi && b < n_bins; ++b) {
         uint32_t n_slots = n_groups;
         cum[0] = 0;
@@ -810,15 +817,21 @@ int64_t oracle_ldsbin_epoch_skips_range(uint64_t seed, uint32_t epoch, uint32_t 
         const uint32_t cold_mass = cum[n_groups];
         const uint32_t hot_lo = hot_off[b], hot_share = hot_off[b + 1] - hot_lo;
         const uint32_t n_draws = n_slots ? cold_mass + hot_share : 0u;
-        if (!n_slots) skipped += cold_mass + hot_share;
+        if (!n_slots && s_begin == 0) skipped += cold_mass + hot_share;  /* (a bin without items: counted by the epoch's first launch) */
         total += cold_mass + hot_share;
-        for (uint32_t local = 0; local < n_draws; ++local) {
+        uint32_t d_lo = 0, d_hi = n_draws;
+        if (nnz) {
+            d_lo = (uint32_t)(((unsigned __int128)n_draws * s_begin) / nnz);
+            if (s_begin + n < nnz) d_hi = (uint32_t)(((unsigned __int128)n_draws * (s_begin + n)) / nnz);
+        }
+        for (uint32_t local = d_lo; local < d_hi; ++local) {
             uint32_t w[4];
             oracle_philox4x32(local, b, epoch, 0x20u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
             const uint32_t r_pos = lemire_bounded2(w[0], w[1], n_draws);
             uint32_t s_j, excl = 0, excl_lo = 0xffffffffu;
             int32_t u, i;
-            if (r_pos < cold_mass) {
+            const int from_hot_list = r_pos >= cold_mass;
+            if (!from_hot_list) {
                 uint32_t lo = 0, hi = n_slots;
                 while (hi - lo > 1) {
                     const uint32_t mid = (lo + hi) >> 1;
@@ -857,11 +870,89 @@ int64_t oracle_ldsbin_epoch_skips_range(uint64_t seed, uint32_t epoch, uint32_t 
             if (csr_has(indices, indptr[u], indptr[u + 1], j)) { ++skipped; continue; }
             if (pos_count) ++pos_count[i];
             if (neg_count) ++neg_count[j];
+            if (kept < out_cap) {
+                if (out_u) out_u[kept] = u;
+                if (out_i) out_i[kept] = i;
+                if (out_j) out_j[kept] = j;
+                if (out_bin) out_bin[kept] = (int32_t)b;
+                if (out_hot) out_hot[kept] = (uint8_t)from_hot_list;
+            }
+            ++kept;
         }
     }
     free(item); free(cp); free(cum); free(hot); free(cold_all); free(hot_off);
     if (n_draws_out) *n_draws_out = total;
+    if (n_out) *n_out = kept;
     return skipped;
+}
+
+/* the skip and touch counters of whole bins: the loop above over every draw of the bins [b_lo, b_hi) */
+int64_t oracle_ldsbin_epoch_skips_range(uint64_t seed, uint32_t epoch, uint32_t key, uint32_t n_bins, uint32_t n_items,
+                                        uint32_t n_hot, uint32_t n_strata, uint32_t hot_cost_x16, const int32_t *rank_item,
+                                        const int32_t *cptr, const int32_t *cusers,
+                                        const int32_t *hot_u, const int32_t *hot_i, uint32_t n_hot_inter, const int32_t *indptr,
+                                        const int32_t *indices, int64_t *n_draws_out, int64_t *pos_count, int64_t *neg_count,
+                                        int neg_pop, uint32_t b_lo, uint32_t b_hi) {
+    return oracle_ldsbin_draws(seed, epoch, key, n_bins, n_items, n_hot, n_strata, hot_cost_x16, rank_item, cptr, cusers, hot_u,
+                               hot_i, n_hot_inter, indptr, indices, n_draws_out, pos_count, neg_count, neg_pop, b_lo, b_hi, 0u, 0u,
+                               0u, NULL, NULL, NULL, NULL, NULL, 0, NULL);
+}
+
+/* The BPR update of a list of triplets in float64, one after another in `order` (indices into the list): the float64
+ * reference of a hogwild launch's arithmetic under ONE order of application (oracle/bpr_step_oracle.py `sequential`).
+ * All five deltas of a triplet come from the values before it, like bpr_step_f64 above. */
+void oracle_bpr_apply_seq_f64(const int64_t *u, const int64_t *i, const int64_t *j, const int64_t *order, int64_t n,
+                              double *U, double *V, double *B, int k, double lr, double reg, int use_bias) {
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t s = order[t];
+        double *pu = U + u[s] * k, *pi = V + i[s] * k, *pj = V + j[s] * k;
+        double x = B[i[s]] - B[j[s]];
+        for (int f = 0; f < k; ++f) x += pu[f] * (pi[f] - pj[f]);
+        const double z = 1.0 / (1.0 + exp(x));
+        for (int f = 0; f < k; ++f) {
+            const double uf = pu[f], vi = pi[f], vj = pj[f];
+            pu[f] = uf + lr * (z * (vi - vj) - reg * uf);
+            pi[f] = vi + lr * (z * uf - reg * vi);
+            pj[f] = vj + lr * (-z * uf - reg * vj);
+        }
+        if (use_bias) {
+            B[i[s]] += lr * (z - reg * B[i[s]]);
+            B[j[s]] += lr * (-z - reg * B[j[s]]);
+        }
+    }
+}
+
+/* The same deltas, every triplet's from the float32 START tables, summed per row in float64 (`jacobi` there): sums, per-row
+ * touch counts and path lengths (sum over a row's triplets of the Euclidean norm of its delta), scores and sigmoids.  The
+ * output arrays arrive zeroed; biases are touched only with use_bias. */
+void oracle_bpr_jacobi_f64(const int64_t *u, const int64_t *i, const int64_t *j, int64_t n, const float *U, const float *V,
+                           const float *B, int k, double lr, double reg, int use_bias, double *sU, double *sV, double *sB,
+                           double *pU, double *pV, double *pB, int64_t *tU, int64_t *tV, int64_t *tB, double *x_out,
+                           double *z_out) {
+    for (int64_t t = 0; t < n; ++t) {
+        const float *pu = U + u[t] * k, *pi = V + i[t] * k, *pj = V + j[t] * k;
+        double *su = sU + u[t] * k, *si = sV + i[t] * k, *sj = sV + j[t] * k;
+        const double bi = B[i[t]], bj = B[j[t]];
+        double x = bi - bj;
+        for (int f = 0; f < k; ++f) x += (double)pu[f] * ((double)pi[f] - (double)pj[f]);
+        const double z = 1.0 / (1.0 + exp(x));
+        double nu2 = 0, ni2 = 0, nj2 = 0;
+        for (int f = 0; f < k; ++f) {
+            const double uf = pu[f], vi = pi[f], vj = pj[f];
+            const double du = lr * (z * (vi - vj) - reg * uf), di = lr * (z * uf - reg * vi), dj = lr * (-z * uf - reg * vj);
+            su[f] += du; si[f] += di; sj[f] += dj;
+            nu2 += du * du; ni2 += di * di; nj2 += dj * dj;
+        }
+        pU[u[t]] += sqrt(nu2); pV[i[t]] += sqrt(ni2); pV[j[t]] += sqrt(nj2);
+        ++tU[u[t]]; ++tV[i[t]]; ++tV[j[t]];
+        if (use_bias) {
+            const double di = lr * (z - reg * bi), dj = lr * (-z - reg * bj);
+            sB[i[t]] += di; sB[j[t]] += dj;
+            pB[i[t]] += fabs(di); pB[j[t]] += fabs(dj);
+            ++tB[i[t]]; ++tB[j[t]];
+        }
+        x_out[t] = x; z_out[t] = z;
+    }
 }
 
 int oracle_num_threads(void) {

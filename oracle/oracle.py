@@ -117,6 +117,16 @@ def _bind(L):
         L.oracle_ldsbin_epoch_skips.restype = C.c_int64
         L.oracle_ldsbin_epoch_skips_range.argtypes = list(L.oracle_ldsbin_epoch_skips.argtypes) + [C.c_uint32, C.c_uint32]
         L.oracle_ldsbin_epoch_skips_range.restype = C.c_int64
+        L.oracle_ldsbin_draws.argtypes = list(L.oracle_ldsbin_epoch_skips_range.argtypes) + [C.c_uint64] * 3 + [C.c_void_p] * 5 + [
+            C.c_int64, C.POINTER(C.c_int64)]
+        L.oracle_ldsbin_draws.restype = C.c_int64
+        f64p_ = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+        L.oracle_bpr_apply_seq_f64.argtypes = [i64p, i64p, i64p, i64p, C.c_int64, f64p_, f64p_, f64p_, C.c_int, C.c_double,
+                                               C.c_double, C.c_int]
+        L.oracle_bpr_apply_seq_f64.restype = None
+        L.oracle_bpr_jacobi_f64.argtypes = [i64p, i64p, i64p, C.c_int64, f32p, f32p, f32p, C.c_int, C.c_double, C.c_double,
+                                            C.c_int] + [f64p_] * 6 + [i64p] * 3 + [f64p_] * 2
+        L.oracle_bpr_jacobi_f64.restype = None
         L.oracle_num_threads.restype = C.c_int
         L.oracle_sizeof_mt.restype = C.c_int
     return L
@@ -565,3 +575,139 @@ def hogwild_sample_owned(seed, epoch, wave_id, length, n_neg, lo, hi):
     lib().oracle_hogwild_sample_owned(int(seed), int(epoch), int(wave_id), int(length), int(n_neg), int(lo), int(hi),
                                       r, jj)
     return r, jj
+
+
+def bpr_apply_seq_f64(trip, order, U, V, B, lr, reg, use_bias):
+    """float64 tables (modified in place) after the triplets' updates, one after another in `order`"""
+    u, i, j = (np.ascontiguousarray(a, np.int64) for a in trip)
+    order = np.ascontiguousarray(order, np.int64)
+    assert U.dtype == V.dtype == B.dtype == np.float64 and len(order) <= len(u)
+    lib().oracle_bpr_apply_seq_f64(u, i, j, order, len(order), U, V, B, U.shape[1], float(lr), float(reg), int(bool(use_bias)))
+
+
+def bpr_jacobi_f64(trip, tables, lr, reg, use_bias):
+    """every triplet's deltas from the float32 start tables, summed per row in float64: {"U" | "V" | "B": dict(sum, touches,
+    path), "x", "z"} (oracle/bpr_step_oracle.py `jacobi`)"""
+    u, i, j = (np.ascontiguousarray(a, np.int64) for a in trip)
+    U, V, B = (np.ascontiguousarray(t, np.float32) for t in tables)
+    out = {tab: dict(sum=np.zeros(t.shape), touches=np.zeros(len(t), np.int64), path=np.zeros(len(t)))
+           for tab, t in (("U", U), ("V", V), ("B", B))}
+    out["x"], out["z"] = np.empty(len(u)), np.empty(len(u))
+    lib().oracle_bpr_jacobi_f64(u, i, j, len(u), U, V, B, U.shape[1], float(lr), float(reg), int(bool(use_bias)),
+                                *[out[tab]["sum"] for tab in "UVB"], *[out[tab]["path"] for tab in "UVB"],
+                                *[out[tab]["touches"] for tab in "UVB"], out["x"], out["z"])
+    return out
+
+
+def hogwild_ownership(indptr, indices, n_waves):
+    """CPU restatement of the user-row ownership tables (csrc/bpr.hip build_ownership): (wave_ptr, own_u, own_i) as
+    BprTrainer.debug_ownership() returns them.  Users with more than nnz / n_waves / 2 interactions are shared (own_u = ~u,
+    their interactions dealt to the waves in equal blocks); the others go whole, heaviest first, to the least loaded wave."""
+    import heapq
+
+    indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices, np.int32)
+    nnz, W = len(indices), int(n_waves)
+    deg = np.diff(indptr)
+    cap = max(1, nnz // W // 2)
+    n_shared = int(deg[deg > cap].sum())
+    blk = (n_shared + W - 1) // W
+    load = [max(0, min(blk, n_shared - w * blk)) if blk > 0 else 0 for w in range(W)]
+    excl = np.flatnonzero((deg > 0) & (deg <= cap))
+    excl = excl[np.argsort(-deg[excl], kind="stable")]
+    heap = [(load[w], w) for w in range(W)]
+    heapq.heapify(heap)
+    owner = np.full(len(deg), -1, np.int64)
+    for usr in excl:
+        ld, w = heapq.heappop(heap)
+        owner[usr] = w
+        load[w] = ld + int(deg[usr])
+        heapq.heappush(heap, (load[w], w))
+    wave_ptr = np.concatenate([[0], np.cumsum(load)]).astype(np.int64)
+    assert wave_ptr[-1] == nnz
+    users = np.repeat(np.arange(len(deg), dtype=np.int64), deg)
+    shared = (deg > cap)[users]
+    wave = owner[users]
+    wave[shared] = np.arange(n_shared) // max(blk, 1)
+    # within a wave: shared positions and exclusive users interleave in user order, exactly as one pass over the users fills them
+    order = np.argsort(wave, kind="stable")
+    own_u = np.where(shared, ~users, users)[order].astype(np.int32)
+    return wave_ptr, own_u, indices[order].astype(np.int32)
+
+
+def _csr_has(indptr, indices, n_items, u, j):
+    """membership of (u, j) in a CSR matrix whose rows hold sorted columns, for arrays of pairs"""
+    rows = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    keys = rows * int(n_items) + np.asarray(indices, np.int64)
+    q = np.asarray(u, np.int64) * int(n_items) + np.asarray(j, np.int64)
+    pos = np.minimum(np.searchsorted(keys, q), len(keys) - 1)
+    return keys[pos] == q
+
+
+def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, neg_pop=False, ownership=None, n_bins=None,
+                     hot_x1000=75, share=None, strata_groups=16, hot_cost_x16=32, tables=None):
+    """The non-skipped (u, i, j) that ONE hogwild launch applies — cornac_hip_bpr_hogwild_enqueue(n) at sample offset
+    s_begin of `epoch`, s_begin + n <= nnz — from the restatements of the device samplers above; integer work, exact.
+
+      form "fused"   samples [s_begin, s_begin + n) of hogwild_sample, in sample order
+      form "owned"   the tiles [own_tmax s_begin / nnz, own_tmax (s_begin + n) / nnz) of every wave's slice
+                     (hogwild_sample_owned), wave by wave; ownership = BprTrainer.debug_ownership()
+      form "ldsbin"  the draws [n_b s_begin / nnz, n_b (s_begin + n) / nnz) of every bin b (resident and passing bins:
+                     the caller names n_bins and, for passing bins, share), bin by bin
+
+    Returns a dict: u, i, j (int64 arrays, the restatement's order), skipped (the launch's skip count); "ldsbin" adds bin
+    (the bin that drew each triplet) and hot (its positive came from the hot list); "owned" adds shared (its user is
+    split over the waves: atomics on its row)."""
+    indptr = np.ascontiguousarray(indptr, np.int32)
+    indices = np.ascontiguousarray(indices, np.int32)
+    nnz, s_begin, n = len(indices), int(s_begin), int(n)
+    assert 0 <= s_begin and n >= 0 and s_begin + n <= nnz
+    if form == "ldsbin":
+        t = tables if tables is not None else ldsbin_tables(indptr, indices, n_items, n_bins, hot_x1000, share)
+        key = int(lib().oracle_ldsbin_key(int(seed), int(epoch)))
+        cap = n + 2 * int(n_bins) + 8
+        u, i, j, b = (np.empty(cap, np.int32) for _ in range(4))
+        hot = np.empty(cap, np.uint8)
+        draws, kept = C.c_int64(), C.c_int64()
+        skipped = lib().oracle_ldsbin_draws(int(seed), int(epoch), key, int(n_bins), int(n_items), int(t["n_hot"]),
+                                            int(ldsbin_n_strata(n_items, n_bins, strata_groups)), int(hot_cost_x16),
+                                            t["rank_item"], t["cptr"], t["cusers"], t["hot_u"], t["hot_i"],
+                                            int(t["n_hot_inter"]), t["indptr"], t["indices"], C.byref(draws), None, None,
+                                            int(bool(neg_pop)), 0, int(n_bins), s_begin, n, nnz, u.ctypes.data, i.ctypes.data,
+                                            j.ctypes.data, b.ctypes.data, hot.ctypes.data, cap, C.byref(kept))
+        m = int(kept.value)
+        assert m <= cap and draws.value == nnz
+        return dict(u=u[:m].astype(np.int64), i=i[:m].astype(np.int64), j=j[:m].astype(np.int64), skipped=int(skipped),
+                    bin=b[:m].astype(np.int64), hot=hot[:m].astype(bool))
+    n_neg = nnz if neg_pop else int(n_items)
+    if form == "fused":
+        user_ids = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+        ii, jj = hogwild_sample(seed, epoch, s_begin, n, nnz, n_neg)
+        u, i = user_ids[ii], indices[ii].astype(np.int64)
+        shared = None
+    elif form == "owned":
+        wave_ptr, own_u, own_i = ownership
+        lens = np.diff(wave_ptr)
+        tmax = int((lens.max() + 63) // 64)
+        lo_tile = tmax * s_begin // nnz
+        hi_tile = tmax if s_begin + n >= nnz else tmax * (s_begin + n) // nnz
+        us, is_, jjs = [], [], []
+        for w in np.flatnonzero(lens > 0):
+            lo, hi = min(int(lens[w]), lo_tile * 64), min(int(lens[w]), hi_tile * 64)
+            if hi <= lo:
+                continue
+            r, jw = hogwild_sample_owned(seed, epoch, int(w), int(lens[w]), n_neg, lo, hi)
+            us.append(own_u[wave_ptr[w] + r])
+            is_.append(own_i[wave_ptr[w] + r])
+            jjs.append(jw)
+        cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, np.int64)
+        u, i, jj = cat(us), cat(is_), cat(jjs)
+        shared = u < 0
+        u = np.where(shared, ~u, u)
+    else:
+        raise ValueError("form is 'fused', 'owned' or 'ldsbin': %r" % (form,))
+    j = indices[jj].astype(np.int64) if neg_pop else jj
+    keep = ~_csr_has(indptr, indices, n_items, u, j)
+    out = dict(u=u[keep], i=i[keep], j=j[keep], skipped=int((~keep).sum()))
+    if shared is not None:
+        out["shared"] = shared[keep]
+    return out

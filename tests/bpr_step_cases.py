@@ -1,0 +1,300 @@
+"""Inputs, references and checks of the hogwild BPR step tests, in ONE place: tests/test_bpr_step_gpu.py runs the cases on
+the device, tests/test_bpr_step_cpu.py proves — from the restatements and the float64 step alone — that every case is a
+fair test, that the tolerances below follow their rules, and that the checks reject nine deliberately wrong updates.
+
+A case = Zipf interactions + normal tables with real scores (z well away from 0.5) + ONE launch of `n` samples at sample
+offset `s_begin` of epoch 0, whose non-skipped triplets oracle.hogwild_triplets names before anything runs.  The launch is
+made three times from the same start tables:
+
+  Z  lr = 0             tables bit-identical; skip counter == the restatement's; `correct` == #(x > 0) in float64, give or
+                        take the triplets whose |x| is below the float32 score's a-priori error bound
+  A  lr = 0.05          rows of CLEAN triplets (no row shared with another triplet of the launch) == the float64 step
+     reg = 0.01         within T_CLEAN; rows no triplet touches (those beyond n_items, every bias without use_bias) bit-identical
+  B  lr = 2^-12         EVERY touched row: |got - start - jacobi sum| <= C[case] x path + floor (Euclidean over the row),
+     reg = 0.01         path = sum over the row's triplets of |delta|, floor = touches x ulp(max |row|) / 2 x sqrt(k)
+
+T_CLEAN.  Rule: 4 x the largest |float32 step - float64 step| over the clean rows of all cases (the device sums the dot
+product in DPP / butterfly order and uses __expf and __frcp_rn), rounded up to one significant digit.
+
+C[case].  Rule: 4 x the largest |sequential - jacobi| / path over all touched rows and three orders of application (the
+restatement's and two seeded permutations), float64, rounded up to one significant digit.  It is the share of a row's
+path by which ANY order of exact updates may differ from the Jacobi sum, so it bounds a correct kernel whatever its
+scheduling; a lost or doubled update moves a row by path / touches, visible where that exceeds 2 x the tolerance.
+tests/test_bpr_step_cpu.py asserts both rules and prints every figure.
+"""
+import functools
+
+import numpy as np
+
+from cornac_amd import _lib, synth
+from oracle import bpr_step_oracle as step
+from oracle import oracle as orc
+
+MI355X_CUS = 256
+LR_A, LR_B, REG = 0.05, 2.0 ** -12, 0.01
+
+# ---- measured (tests/test_bpr_step_cpu.py prints the CPU figures, tests/test_bpr_step_gpu.py the MI355X ones) ------------
+# float32 step vs float64 step over the clean rows of all cases: 1.17e-7 (fused_k3, whose rows reach 2.1: ulp / 2 = 1.2e-7;
+#   5e-8 .. 1e-7 elsewhere)  ->  T_CLEAN = 5e-7.
+# |sequential - jacobi| / path, three orders: 0.0027 .. 0.0054 for the 2 048-sample launches with biases (0.0007 .. 0.0011
+#   without: the bias deltas are what moves a score most), 0.030 / 0.035 passing, 0.035 wide, 0.0053 / 0.0058 owned (one
+#   tile of each of 4 096 / 6 144 waves: 262 138 / 393 207 triplets)  ->  C below.
+# MI355X, launch Z: `correct` inside the float64 interval in every case (the interval is one number in 21 of 27 cases).
+# MI355X, launch A, largest |got - float64 step| over clean rows: U 6.0e-8, V 1.17e-7 (fused_k3), B 8.6e-8 — the float32
+#   step's own error, a quarter of T_CLEAN.
+# MI355X, launch B, largest error / tolerance over touched rows: U 0.18, V 0.26, B 0.41 (owned_k100; 0.39 lds_k64) — the
+#   device is one more order of application, a quarter of C like the three measured ones.  Owned kernel, error / PATH:
+#   U 0.0035 / 0.0046, V 0.0080 / 0.0058, B 0.033 / 0.022 (k = 64 / 100).  The bias figure belongs to rows touched ONCE whose
+#   delta lr (z - reg b) is small (z = 0.01: path 1e-6) beside the rounding of its one float32 add onto |b| = 1.4 (3.4e-8,
+#   under ulp / 2 = 6e-8): that is the floor term of the tolerance; net of it the bias rows lie within 0.0041 / 0.0049 of
+#   their path, like U, V and the float64 orders.
+T_CLEAN = 5e-7
+C = {
+    "fused_k3": 0.03, "fused_k7": 0.02, "fused_k16": 0.02, "fused_k20": 0.02,
+    "fused_k50": 0.02, "fused_k100": 0.02, "fused_k192": 0.02, "fused_k200": 0.02,
+    "fused_generic_k300": 0.02, "fused_vec4_k12": 0.02, "fused_vec4_k64": 0.02, "fused_dense_bias_k50": 0.02,
+    "fused_nobias_k100": 0.003, "fused_pop_k16": 0.01, "lds_k40": 0.02, "lds_k64": 0.02,
+    "lds_k100": 0.02, "lds_k192": 0.02, "lds_k200": 0.02, "lds_nobias_k64": 0.005,
+    "lds_pop_k100": 0.007, "lds_partial_k64": 0.02, "lds_wide_k64": 0.2, "pass_k128": 0.2, "pass_k64": 0.2,
+    "owned_k64": 0.03, "owned_k100": 0.03,
+}
+
+
+def _fused(k, flags=0, **kw):
+    return dict(dict(form="fused", k=k, nu=20_000, ni=30_720, nnz=300_000, zipf=0.8, n=2048,
+                     flags=_lib.FORM_FUSED | _lib.HOG_NO_OWNERSHIP | flags), **kw)
+
+
+def _owned(k, **kw):
+    return dict(dict(form="owned", k=k, nu=200_000, ni=400_000, nnz=524_288, zipf=0.3, n=None, flags=_lib.HOG_FUSED_OPT_OUT,
+                     clean_share=False), **kw)
+
+
+def _lds(k, **kw):
+    return dict(dict(form="ldsbin", k=k, nu=20_000, ni=30_720, nnz=300_000, zipf=0.8, n=2048, flags=_lib.FORM_LDSBIN), **kw)
+
+
+# One case per kernel instantiation the dispatchers return (csrc/bpr.hip pick_hogwild_kernel, pick_ldsbin_kernel).
+SPECS = {
+    # fused, unowned: every (G, R) of the row-wise kernel, the generic kernel, two float4 layouts, the switches
+    "fused_k3": _fused(3), "fused_k7": _fused(7), "fused_k16": _fused(16), "fused_k20": _fused(20),
+    "fused_k50": _fused(50), "fused_k100": _fused(100), "fused_k192": _fused(192), "fused_k200": _fused(200),
+    "fused_generic_k300": _fused(300),
+    "fused_vec4_k12": _fused(12, _lib.HOG_VEC4_LAYOUT), "fused_vec4_k64": _fused(64, _lib.HOG_VEC4_LAYOUT),
+    "fused_dense_bias_k50": _fused(50, _lib.HOG_DENSE_BIAS),
+    "fused_nobias_k100": _fused(100, use_bias=False),
+    "fused_pop_k16": _fused(16, neg_pop=True, ni=61_440, n=1536),  # (as lds_pop_k100 below)
+    # LDS bins, resident: R = 1..4, without biases, popularity negatives, a partial last group (30 733 = 120 x 256 + 13)
+    "lds_k40": _lds(40), "lds_k64": _lds(64), "lds_k100": _lds(100), "lds_k192": _lds(192), "lds_k200": _lds(200),
+    "lds_nobias_k64": _lds(64, use_bias=False),
+    # (popularity negatives land on the popular items again and again: a larger catalogue and a shorter launch keep a third clean)
+    "lds_pop_k100": _lds(100, neg_pop=True, ni=61_440, n=1536),
+    "lds_partial_k64": _lds(64, ni=30_733),
+    # 64-draw tiles (csrc/bpr_ldsbin.inc ldsbin_launch_range: >= 8 192 draws per bin and launch): the rest of an epoch of
+    # 2.4 M interactions, flat distributions so that C stays at 0.2 (at Zipf 0.8: 3).  No triplet of such a launch is clean
+    # and a row is touched 100 times and more, so only launch B applies and it shows wrong factors and lost SHARES of a
+    # row's updates, not a single lost update (visibility 0).
+    "lds_wide_k64": _lds(64, nu=100_000, zipf=0.3, user_sigma=0.5, nnz=2_400_000, n=2_400_000 - 12_345, clean_share=False,
+                         only_b=True),
+    # LDS bins, passing: max_rounds = 1 turns a catalogue just past one round of resident bins into passing bins.  A
+    # passing launch is at least a quarter of an epoch (csrc/bpr.hip ldsbin_can_run): 75 000 samples over these small
+    # catalogues leave few clean triplets, so launch A's share condition is not asked of them (clean_share=False) — the
+    # clean triplets that exist are checked all the same — and launch B carries the form.  Next to none of the clean
+    # triplets has a hot positive (1 and 0 do): the 10 700 hot positives of such a launch fall on 950 hot items, a median of
+    # 14 touches on such a row, and the launch cannot be shorter.
+    "pass_k128": _lds(128, nu=100_000, ni=80_000, nnz=262_144, zipf=0.6, user_sigma=0.5, n=65_536, max_rounds=1, clean_share=False),
+    "pass_k64": _lds(64, nu=100_000, ni=80_000, nnz=262_144, zipf=0.6, user_sigma=0.5, n=65_536, max_rounds=1, clean_share=False),
+    # fused, OWNED (k > 32, nnz >= 8 workgroups x 4 waves x 64 samples per CU): every wave draws from its own users' slice,
+    # exclusive users take plain stores and users split over the waves ("shared") atomics.  The smallest launch is one
+    # 64-sample tile of EVERY wave of the persistent grid (Case computes n), so no third of it is clean (clean_share=False:
+    # the clean triplets that exist are checked all the same) and launch B carries the form; a flat 200 000 x 400 000
+    # problem keeps the mean touches per row below 4.  `waves`: the persistent grid on an MI355X, 256 CUs x 4 workgroups
+    # x 4 waves at k = 64 (R = 1) and x 6 x 4 at k = 100 (R = 2), the occupancy of the two instantiations; the device test
+    # takes the count from debug_ownership() and rebuilds the case if the device runs another grid.
+    "owned_k64": _owned(64, waves=4096), "owned_k100": _owned(100, waves=6144),
+}
+NAMES = list(SPECS)
+
+
+def ldsbin_plan(ni, nnz, k, cus=MI355X_CUS, min_candidates=48, max_rounds=4, pass_min_draws_x100=200):
+    """csrc/bpr.hip ldsbin_plan restated (defaults of the pass config), LDS byte count included: dict(bins, cap, passing) or
+    None.  tests/test_bpr_step_gpu.py holds it against ldsbin_stats() before it launches; the CPU test has no device to
+    ask, so a change of the kernel's plan that this function misses shows there, on the device, not on the CPU."""
+    if k > 256 or nnz < cus * 16 * 64:
+        return None
+    kp = (k + 63) // 64 * 64
+    lds = lambda cap, waves: (cap * (kp + 5) + 1) * 4 + waves * 3 * 64 * 4
+    for rounds in range(1, max_rounds + 1):
+        bins = cus * rounds
+        cap = -(-ni // bins)
+        if cap < min_candidates:
+            return None
+        if lds(cap, 16) <= 96 * 1024:
+            return dict(bins=bins, cap=cap, passing=False)
+    if nnz * 100 < ni * pass_min_draws_x100:
+        return None
+    cap = (64 * 1024 - (4 + 8 * 3 * 64 * 4)) // ((kp + 5) * 4)
+    if cap < min_candidates:
+        return None
+    bins = -(-(-(-ni // cap)) // cus) * cus
+    cap = -(-ni // bins)
+    if cap < min_candidates:
+        return None
+    return dict(bins=bins, cap=cap, passing=True)
+
+
+@functools.lru_cache(maxsize=4)
+def _data(nu, ni, nnz, zipf, user_sigma=1.0):
+    users, items = synth.zipf_interactions(nu, ni, nnz, zipf, 11, user_sigma)
+    return synth.csr_from_sorted(users, items, nu)
+
+
+def _tables(name, nu, total_items, k):
+    """normal tables whose scores have unit spread whatever k (x = u.(vi - vj) + bi - bj: variance 2 k s^4 + 2 s_b^2 = 1
+    with s_b = 0.5): float32 values, so exactly representable on the device"""
+    rs = np.random.RandomState(sum(map(ord, name)) + 1000 * k)
+    s = (0.25 / k) ** 0.25
+    return (rs.normal(0, s, (nu, k)).astype(np.float32), rs.normal(0, s, (total_items, k)).astype(np.float32),
+            rs.normal(0, 0.5, total_items).astype(np.float32))
+
+
+class Case:
+    """the inputs of one case and, computed once and never modified, its triplets and float64 references"""
+
+    def __init__(self, name, cus=MI355X_CUS, waves=None):
+        sp = dict(dict(use_bias=True, neg_pop=False, s_begin=12_345, seed=0x5EED0000 + len(name), max_rounds=4,
+                       min_candidates=48, clean_share=True, only_b=False, user_sigma=1.0), **SPECS[name])
+        self.name, self.spec = name, sp
+        for key, v in sp.items():
+            setattr(self, key, v)
+        self.total_items = self.ni + 37  # item rows beyond the trained range: no launch may touch them
+        self.indptr, self.indices = _data(self.nu, self.ni, self.nnz, self.zipf, self.user_sigma)
+        self.tables = _tables(name, self.nu, self.total_items, self.k)
+        self.neg_population = _lib.NEG_POPULARITY if self.neg_pop else _lib.NEG_UNIFORM
+        kw = {}
+        self.plan = self.ownership = None
+        if self.form == "ldsbin":
+            self.plan = ldsbin_plan(self.ni, self.nnz, self.k, cus, self.min_candidates, self.max_rounds)
+            assert self.plan is not None, "%s: no LDS-bin plan" % name
+            kw = dict(n_bins=self.plan["bins"], share=self.nnz / (4.0 * cus) if self.plan["passing"] else None)
+        if self.form == "owned":
+            # the smallest launch of this form: one 64-sample tile of every wave (csrc/bpr.hip: a launch covers the tiles
+            # [tmax s_begin / nnz, tmax (s_begin + n) / nnz) of every wave's slice, tmax = the longest slice's tile count)
+            self.ownership = orc.hogwild_ownership(self.indptr, self.indices, waves or self.waves)
+            tmax = int((np.diff(self.ownership[0]).max() + 63) // 64)
+            self.n = -(-self.nnz // tmax) - self.s_begin
+            assert tmax * self.s_begin // self.nnz == 0 and (tmax == 1 or tmax * (self.s_begin + self.n) // self.nnz == 1)
+            kw = dict(ownership=self.ownership)
+        t = orc.hogwild_triplets(self.form, self.seed, 0, self.s_begin, self.n, self.indptr, self.indices, self.ni,
+                                 neg_pop=self.neg_pop, **kw)
+        self.trip = (t["u"], t["i"], t["j"])
+        self.skipped, self.hot, self.bin, self.shared = t["skipped"], t.get("hot"), t.get("bin"), t.get("shared")
+        # launch B: the Jacobi sum of every row; launch A: the float64 step of the clean triplets alone (their rows have no
+        # other delta, so no sum is needed); launch Z: the float64 scores (they do not depend on lr)
+        self.jac = step.jacobi(self.trip, self.tables, LR_B, REG, self.use_bias)
+        for tab in "UVB":
+            for a in self.jac[tab].values():
+                a.setflags(write=False)
+        self.touches = {tab: self.jac[tab]["touches"] for tab in "UVB"}
+        u, i, j = self.trip
+        self.clean = (self.touches["U"][u] == 1) & (self.touches["V"][i] == 1) & (self.touches["V"][j] == 1)
+        cu, ci, cj = (a[self.clean] for a in self.trip)
+        _, _, dU, dVi, dVj, dBi, dBj = step.deltas((cu, ci, cj), *self.tables, LR_A, REG, self.use_bias)
+        cij = np.concatenate([ci, cj])
+        self.clean_rows = {"U": cu, "V": cij, "B": cij}
+        self.clean_want = {tab: start[rows].astype(np.float64) + d for tab, start, rows, d in (
+            ("U", self.tables[0], cu, dU), ("V", self.tables[1], cij, np.concatenate([dVi, dVj])),
+            ("B", self.tables[2], cij, np.concatenate([dBi, dBj])))}
+        self.x, self.z = self.jac["x"], self.jac["z"]
+        self.x_bound = step.score_error_bound(self.trip, self.tables)
+
+    def triplets_of(self, table, row):
+        u, i, j = self.trip
+        return np.flatnonzero(u == row if table == "U" else (i == row) | (j == row))
+
+    def describe(self, table, row):
+        ids = self.triplets_of(table, row)
+        u, i, j = self.trip
+        return "%s: table %s row %d, %d touches, triplets %s" % (
+            self.name, table, row, len(ids), ", ".join("#%d (u %d, i %d, j %d)" % (t, u[t], i[t], j[t]) for t in ids[:8]) +
+            (" ..." if len(ids) > 8 else ""))
+
+
+@functools.lru_cache(maxsize=2)
+def case(name, cus=MI355X_CUS, waves=None):
+    return Case(name, cus, waves)
+
+
+# ---- the checks: `got` = (U, V, B) as the device (or a deliberately wrong reference) returns them --------------------------
+def _untouched_identical(c, launch, got):
+    for tab, start, g in zip("UVB", c.tables, got):
+        same = (g == start).reshape(len(start), -1).all(axis=1) | (c.touches[tab] > 0)
+        assert same.all(), "launch %s changed a row no triplet touches: %s" % (launch, c.describe(tab, int(np.flatnonzero(~same)[0])))
+
+
+def check_z(c, got, correct, skipped):
+    for tab, start, g in zip("UVB", c.tables, got):
+        assert np.array_equal(start, g), "%s: lr = 0 changed table %s" % (c.name, tab)
+    assert skipped == c.skipped, "%s: skip counter %d, restatement %d" % (c.name, skipped, c.skipped)
+    lo, hi = int((c.x > c.x_bound).sum()), int((c.x > -c.x_bound).sum())
+    assert lo <= correct <= hi, "%s: `correct` = %d, float64 scores give %d..%d" % (c.name, correct, lo, hi)
+    return dict(correct=correct, lo=lo, hi=hi)
+
+
+def check_a(c, got):
+    """launch A: clean rows against the float64 step at T_CLEAN, untouched rows bit-identical.  Returns the largest
+    clean-row error per table."""
+    _untouched_identical(c, "A", got)
+    worst = {}
+    for tab, g in zip("UVB", got):
+        rows, want = c.clean_rows[tab], c.clean_want[tab]
+        err = np.abs(g[rows].astype(np.float64) - want).reshape(len(rows), -1).max(axis=1) if len(rows) else np.zeros(0)
+        worst[tab] = float(err.max()) if len(err) else 0.0
+        bad = np.flatnonzero(err > T_CLEAN)
+        assert len(bad) == 0, "launch A, clean row off by %.3g > T_CLEAN = %.3g (%d such rows): %s" % (
+            err[bad[0]], T_CLEAN, len(bad), c.describe(tab, int(rows[bad[0]])))
+    return worst
+
+
+def tolerance_b(c, tab, coeff=None):
+    """per-row tolerance of launch B for one table: C x path + touches x ulp(max |row|) / 2 x sqrt(k)"""
+    coeff = C[c.name] if coeff is None else coeff
+    j = c.jac[tab]
+    start = c.tables["UVB".index(tab)].astype(np.float64).reshape(len(j["touches"]), -1)
+    top = np.maximum(np.abs(start), np.abs(start + j["sum"].reshape(start.shape))).max(axis=1)
+    half_ulp = np.spacing(top.astype(np.float32)).astype(np.float64) / 2
+    return coeff * j["path"] + j["touches"] * half_ulp * np.sqrt(start.shape[1])
+
+
+def check_b(c, got, coeff=None):
+    """launch B: every touched row against the Jacobi sum.  Returns the largest error / tolerance per table."""
+    _untouched_identical(c, "B", got)
+    worst = {}
+    for tab, start, g in zip("UVB", c.tables, got):
+        j = c.jac[tab]
+        rows = np.flatnonzero(j["touches"] > 0)
+        if len(rows) == 0:
+            worst[tab] = 0.0
+            continue
+        moved = g[rows].astype(np.float64) - start[rows].astype(np.float64)
+        err = np.linalg.norm((moved - j["sum"][rows]).reshape(len(rows), -1), axis=1)
+        tol = tolerance_b(c, tab, coeff)[rows]
+        worst[tab] = float((err / tol).max())
+        bad = np.flatnonzero(err > tol)
+        assert len(bad) == 0, "launch B, |got - start - jacobi| = %.3g > %.3g (path %.3g; %d such rows): %s" % (
+            err[bad[0]], tol[bad[0]], j["path"][rows[bad[0]]], len(bad), c.describe(tab, int(rows[bad[0]])))
+    return worst
+
+
+def visibility(c, tab, coeff=None):
+    """share of the touched rows of a table on which ONE lost or doubled update shows: path / touches > 2 x tolerance"""
+    j = c.jac[tab]
+    rows = np.flatnonzero(j["touches"] > 0)
+    if len(rows) == 0:
+        return 1.0
+    return float((j["path"][rows] / j["touches"][rows] > 2 * tolerance_b(c, tab, coeff)[rows]).mean())
+
+
+def round_up_1sig(v):
+    e = np.floor(np.log10(v))
+    return float(np.ceil(v / 10 ** e - 1e-9) * 10 ** e)
