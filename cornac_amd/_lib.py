@@ -62,6 +62,7 @@ SYMBOLS = [
     "cornac_hip_mf_hogwild_form", "cornac_hip_mf_hogwild_stats",
     "cornac_hip_mf_fit_minibatch", "cornac_hip_mf_fit_minibatch_dropout", "cornac_hip_mf_reset_optimizer",
     "cornac_hip_mf_pmf_set_factors", "cornac_hip_mf_pmf_get_factors", "cornac_hip_mf_pmf_fit", "cornac_hip_mf_pmf_form",
+    "cornac_hip_mf_nmf_set_factors", "cornac_hip_mf_nmf_get_factors", "cornac_hip_mf_nmf_fit", "cornac_hip_mf_nmf_form",
     "cornac_hip_scorer_create", "cornac_hip_scorer_destroy", "cornac_hip_scorer_set", "cornac_hip_score_user",
     "cornac_hip_scorer_set_f64", "cornac_hip_score_user_f64",
     "cornac_hip_score_block", "cornac_hip_rank_topk", "cornac_hip_rank_topk_device", "cornac_hip_score_pairs",
@@ -226,6 +227,10 @@ def lib():
         L.cornac_hip_mf_pmf_get_factors.argtypes = [_vp, _vp, _vp]
         L.cornac_hip_mf_pmf_fit.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _vp]
         L.cornac_hip_mf_pmf_form.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cornac_hip_mf_nmf_set_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
+        L.cornac_hip_mf_nmf_get_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
+        L.cornac_hip_mf_nmf_fit.argtypes = [_vp, C.c_int] + [C.c_float] * 6 + [C.c_int, C.c_int, _vp]
+        L.cornac_hip_mf_nmf_form.argtypes = [_vp] + [C.POINTER(C.c_int)] * 3
         L.cornac_hip_wmf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, C.c_int, _i64, _i32, _f32,
                                             C.c_int64]
         L.cornac_hip_wmf_destroy.argtypes = [_vp]
@@ -783,6 +788,38 @@ class MfTrainer:
         form, group = C.c_int(), C.c_int()
         check(lib().cornac_hip_mf_pmf_form(self.h, C.byref(form), C.byref(group)))
         return form.value, group.value
+
+    # ---- NMF on the same handle (float32 tables of its own; the ratings must be stored by user) ---------------------
+    def nmf_set_factors(self, U, V, Bu=None, Bi=None):
+        """float32 U [n_users, k], V [n_items, k]; Bu / Bi: None = zeros"""
+        nu, ni, k = self.shape
+        U, V, Bu, Bi = _f32c(U), _f32c(V), _f32c(Bu), _f32c(Bi)
+        if U.shape != (nu, k) or V.shape != (ni, k):
+            raise ValueError("NMF tables must be %r and %r, got %r and %r" % ((nu, k), (ni, k), U.shape, V.shape))
+        if (Bu is not None and Bu.shape != (nu,)) or (Bi is not None and Bi.shape != (ni,)):
+            raise ValueError("NMF biases must be (%d,) and (%d,)" % (nu, ni))
+        check(lib().cornac_hip_mf_nmf_set_factors(self.h, _ptr(U), _ptr(V), _ptr(Bu), _ptr(Bi)))
+
+    def nmf_get_factors(self):
+        nu, ni, k = self.shape
+        U, V = np.empty((nu, k), np.float32), np.empty((ni, k), np.float32)
+        Bu, Bi = np.empty(nu, np.float32), np.empty(ni, np.float32)
+        check(lib().cornac_hip_mf_nmf_get_factors(self.h, U.ctypes.data, V.ctypes.data, Bu.ctypes.data, Bi.ctypes.data))
+        return U, V, Bu, Bi
+
+    def nmf_fit(self, n_epochs, lr, lambda_u, lambda_v, lambda_bu, lambda_bi, mu, use_bias=False, mode=MODE_HOGWILD):
+        """n_epochs multiplicative-update epochs; the loss of each (float64)"""
+        loss = np.zeros(max(int(n_epochs), 1), np.float64)
+        check(lib().cornac_hip_mf_nmf_fit(self.h, int(n_epochs), lr, lambda_u, lambda_v, lambda_bu, lambda_bi, mu,
+                                          int(bool(use_bias)), int(mode), loss.ctypes.data))
+        return loss[:max(int(n_epochs), 0)]
+
+    def nmf_form(self):
+        """(sum_form, bias_form, rows_split) of the last NMF epoch: 1 ordered / 2 free-order sums; 0 no bias pass /
+        1 dataflow launch / 2 level schedule; rows summed in more than one piece"""
+        o = [C.c_int(), C.c_int(), C.c_int()]
+        check(lib().cornac_hip_mf_nmf_form(self.h, *[C.byref(x) for x in o]))
+        return tuple(x.value for x in o)
 
     def kernel_timing(self, enable=True):
         ms, n = C.c_double(), C.c_int64()

@@ -425,6 +425,19 @@ static int mf_pow2_group(int k) {
 
 using namespace chip;
 
+// NMF (nmf.inc): the segments of one side's rows, and the rows whose partial sums are combined afterwards
+struct NmfSide {
+    DevBuf<int32_t> seg_row, seg_len, seg_dst, c_row, c_slot, c_n;
+    DevBuf<int64_t> seg_beg;
+    int64_t n_seg = 0, n_comb = 0;
+};
+struct NmfPlan {
+    bool built = false;
+    NmfSide side[2];      // users (CSR), items (CSC)
+    DevBuf<float> part;   // partial sums of split rows: [slot][2][k]
+    int rows_split = 0;
+};
+
 struct cornac_hip_mf {
     int device = 0;
     int64_t n_users = 0, n_items = 0, nnz = 0;
@@ -487,6 +500,20 @@ struct cornac_hip_mf {
     DevBuf<double> pmf_U, pmf_V, pmf_cu, pmf_cv, pmf_loss;
     bool pmf_set = false, pmf_chain_refused = false;
     int pmf_form = 0, pmf_group = 0;  // last epoch: 1 dataflow launch / 2 level schedule, ratings per wave pass
+    // NMF (nmf.inc): float32 tables of its own, the four row sums, r_pred per rating; CSR / CSC views of the stored order
+    DevBuf<float> nmf_U, nmf_V, nmf_Bu, nmf_Bi, nmf_unum, nmf_uden, nmf_vnum, nmf_vden, nmf_pred;
+    DevBuf<double> nmf_loss;
+    bool nmf_set = false, nmf_built = false, nmf_levels_built = false, nmf_chain_built = false, nmf_chain_refused = false;
+    std::vector<int64_t> nmf_uptr_h, nmf_iptr_h;
+    DevBuf<int64_t> nmf_uptr, nmf_iptr;
+    DevBuf<int32_t> nmf_uid, nmf_cid, nmf_perm, nmf_cuid, nmf_cseq, nmf_lpos;
+    NmfPlan nmf_plan[2];  // [mode]
+    int nmf_chain_grid = 0;
+    size_t nmf_c_rows = 0;
+    DevBuf<int64_t> nmf_c_wrow_ptr, nmf_c_row_beg, nmf_c_row_end, nmf_c_row_cur;
+    DevBuf<int32_t> nmf_c_row_id;
+    DevBuf<unsigned int> nmf_ver, nmf_abort;
+    int nmf_sum_form = 0, nmf_bias_form = 0, nmf_rows_split = 0;  // last epoch (cornac_hip_mf_nmf_form)
 };
 
 #include "mf_blocks.inc"
@@ -1498,3 +1525,4 @@ int cornac_hip_mf_last_timing(cornac_hip_mf_t h, double *ms4) {
 
 #include "mf_minibatch.inc"
 #include "pmf.inc"
+#include "nmf.inc"

@@ -467,6 +467,38 @@ int cornac_hip_mf_pmf_fit(cornac_hip_mf_t h, int n_epochs, float lr, float reg, 
 /* 1 = dataflow launch, 2 = level schedule, 0 = none yet; *group = ratings per wave pass of the last epoch */
 int cornac_hip_mf_pmf_form(cornac_hip_mf_t h, int *form, int *group);
 
+/* NMF on the same handle: multiplicative updates in float32, tables of their own (the MF and PMF state of the handle is
+ * untouched, and an MF or PMF fit leaves these alone).
+ * Replaces: NMF._fit_sgd(rid, cid, val, user_counts, item_counts, U, V, Bu, Bi)
+ *           cornac/models/nmf/recom_nmf.pyx:182-267 (called from NMF.fit, :162-180, with the CSR of train_set.matrix).
+ * The handle's ratings must be stored by user (rid non-decreasing), as the reference's CSR is: cornac_hip_mf_nmf_fit
+ * refuses any other order.  One epoch, every float32 operation separately rounded:
+ *   r_pred = ((mu + Bu[u]) + Bi[i]) + U[u,0] V[i,0] + ... (index order); error = r - r_pred            (:228-232)
+ *   use_bias: Bu[u] += lr (error - lambda_bu Bu[u]); Bi[i] += lr (error - lambda_bi Bi[i]), in stored order (:236-238)
+ *   U_num += r V, U_den += r_pred V, V_num += r U, V_den += r_pred U from zero                          (:241-245)
+ *   U_den += count_u lambda_u U + 1e-9f; U *= U_num / U_den for the users, then the items (a row without ratings
+ *   becomes zero)                                                                                       (:248-259)
+ *   loss = sum error^2 + lambda_u sum U^2 + lambda_v sum V^2 over the pre-update tables, float32 terms summed in double.
+ * MODE_DETERMINISTIC: every row sum in ascending rating index, r_pred serial in f: the factors are bit-identical to the
+ * source's single-thread float32 loop (its IEEE semantics, every operation separately rounded).
+ * MODE_HOGWILD: rows longer than 256 ratings are summed in pieces of 256 whose partial sums are added in ascending
+ * order, r_pred's dot product is a butterfly: exact sums in another, fixed order — the same bits run to run, one owner
+ * per accumulator row, no float atomics (a prange build of the reference would race on these +=).
+ * The bias pass is sequential-exact in both modes: below 4096 ratings (or after a refused cooperative launch) the level
+ * schedule, above one persistent dataflow launch with the users owned and the item bias handed over by version counters.
+ * Any k >= 1.  The row sums live in registers up to k = 256 (lane groups of pow2 >= k lanes: 8, 4, 2 rows per wave up
+ * to k = 32); beyond that one wave per row keeps them in memory. */
+/* float32 U [n_users,k], V [n_items,k]; Bu [n_users], Bi [n_items] may be NULL: zeros (recom_nmf.pyx:134-145) */
+int cornac_hip_mf_nmf_set_factors(cornac_hip_mf_t h, const float *U, const float *V, const float *Bu, const float *Bi);
+/* any pointer may be NULL */
+int cornac_hip_mf_nmf_get_factors(cornac_hip_mf_t h, float *U, float *V, float *Bu, float *Bi);
+/* n_epochs epochs of recom_nmf.pyx:217-259; mode: CORNAC_HIP_MODE_*; loss_per_epoch [n_epochs] may be NULL */
+int cornac_hip_mf_nmf_fit(cornac_hip_mf_t h, int n_epochs, float lr, float lambda_u, float lambda_v, float lambda_bu,
+                          float lambda_bi, float mu, int use_bias, int mode, double *loss_per_epoch);
+/* the kernels of the last epoch (0 = none yet): *sum_form 1 ordered / 2 free-order; *bias_form 0 none / 1 dataflow launch /
+ * 2 level schedule (the prange body's bias lines, :236-238); *rows_split rows summed in more than one piece */
+int cornac_hip_mf_nmf_form(cornac_hip_mf_t h, int *sum_form, int *bias_form, int *rows_split);
+
 /* Minibatch path with dense optimisers on the same handle.
  * Replaces: backend_pt.learn(model, train_set, n_epochs, batch_size, learning_rate, reg, optimizer)
  *           cornac/models/mf/backend_pt.py:67-106 and the forward of backend_pt.MF (:56-65), selected by
