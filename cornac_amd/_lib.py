@@ -59,7 +59,7 @@ SYMBOLS = [
     "cornac_hip_mf_create", "cornac_hip_mf_destroy", "cornac_hip_mf_set_factors", "cornac_hip_mf_get_factors",
     "cornac_hip_mf_fit", "cornac_hip_mf_bind_items", "cornac_hip_mf_bind_users", "cornac_hip_mf_set_stream", "cornac_hip_mf_epoch_enqueue",
     "cornac_hip_mf_sync", "cornac_hip_mf_fit_sgd", "cornac_hip_mf_last_timing",
-    "cornac_hip_mf_hogwild_form", "cornac_hip_mf_hogwild_stats",
+    "cornac_hip_mf_hogwild_form", "cornac_hip_mf_hogwild_stats", "cornac_hip_mf_debug_split", "cornac_hip_mf_debug_ownership",
     "cornac_hip_mf_fit_minibatch", "cornac_hip_mf_fit_minibatch_dropout", "cornac_hip_mf_reset_optimizer",
     "cornac_hip_mf_pmf_set_factors", "cornac_hip_mf_pmf_get_factors", "cornac_hip_mf_pmf_fit", "cornac_hip_mf_pmf_form",
     "cornac_hip_mf_nmf_set_factors", "cornac_hip_mf_nmf_get_factors", "cornac_hip_mf_nmf_fit", "cornac_hip_mf_nmf_form",
@@ -259,6 +259,8 @@ def lib():
         L.cornac_hip_mf_last_timing.argtypes = [_vp, C.POINTER(C.c_double)]
         L.cornac_hip_mf_hogwild_form.argtypes = [_vp, C.c_int]
         L.cornac_hip_mf_hogwild_stats.argtypes = [_vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_mf_debug_split.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp, _vp]
+        L.cornac_hip_mf_debug_ownership.argtypes = [_vp, C.POINTER(C.c_int64), _vp, _vp, _vp]
         L.cornac_hip_scorer_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, C.c_int]
         L.cornac_hip_scorer_destroy.argtypes = [_vp]
         L.cornac_hip_scorer_set.argtypes = [_vp, _f32, _f32, _vp, _vp]
@@ -834,6 +836,28 @@ class MfTrainer:
         o = (C.c_int64 * 4)()
         check(lib().cornac_hip_mf_hogwild_stats(self.h, o))
         return {"form_used": o[0], "tiles": o[1], "rows_per_bin": o[2], "gave_up": bool(o[3])}
+
+    def debug_split(self):
+        """(split_item, split_ptr): the item rows that train through copies and the copies of each (ids n_items +
+        split_ptr[j] .. n_items + split_ptr[j + 1]); empty / [0] when no row is split or nothing has been launched"""
+        ns, nv = C.c_int64(), C.c_int64()
+        check(lib().cornac_hip_mf_debug_split(self.h, C.byref(ns), C.byref(nv), None, None))
+        items, ptr = np.empty(ns.value, np.int32), np.zeros(ns.value + 1, np.int32)
+        if ns.value:
+            check(lib().cornac_hip_mf_debug_split(self.h, C.byref(ns), C.byref(nv), items.ctypes.data, ptr.ctypes.data))
+        return items, ptr
+
+    def debug_ownership(self):
+        """(wave_ptr, own_u, own_i) of the fused kernel's user-row ownership, or None if the last hogwild launch was not
+        an owned one"""
+        w = C.c_int64()
+        check(lib().cornac_hip_mf_debug_ownership(self.h, C.byref(w), None, None, None))
+        if w.value == 0:
+            return None
+        wp = np.empty(w.value + 1, np.int64)
+        ou, oi = np.empty(len(self.val), np.int32), np.empty(len(self.val), np.int32)
+        check(lib().cornac_hip_mf_debug_ownership(self.h, C.byref(w), wp.ctypes.data, ou.ctypes.data, oi.ctypes.data))
+        return wp, ou, oi
 
     def last_timing(self):
         t = (C.c_double * 4)()

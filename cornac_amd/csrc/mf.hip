@@ -1515,6 +1515,36 @@ int cornac_hip_mf_hogwild_stats(cornac_hip_mf_t h, int64_t *out4) {
     });
 }
 
+// ---- read-only test hooks: what the handle decided (tests/test_mf_step_gpu.py holds them against their restatements) ----
+int cornac_hip_mf_debug_split(cornac_hip_mf_t h, int64_t *n_split, int64_t *n_virtual, int32_t *split_item, int32_t *split_ptr) {
+    return guarded([&] {
+        mf_check(h);
+        REQUIRE(n_split && n_virtual, "n_split and n_virtual are required");
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        *n_split = h->split_built ? h->mb_n_split : 0;
+        *n_virtual = h->split_built ? h->mb_n_virtual : 0;
+        if (*n_split == 0) return;
+        if (split_item) HIP_CHECK(hipMemcpy(split_item, h->mb_split_item.p, sizeof(int32_t) * (size_t)h->mb_n_split, hipMemcpyDeviceToHost));
+        if (split_ptr) HIP_CHECK(hipMemcpy(split_ptr, h->mb_split_ptr.p, sizeof(int32_t) * ((size_t)h->mb_n_split + 1), hipMemcpyDeviceToHost));
+    });
+}
+
+int cornac_hip_mf_debug_ownership(cornac_hip_mf_t h, int64_t *n_waves, int64_t *wave_ptr, int32_t *own_u, int32_t *own_i) {
+    return guarded([&] {
+        mf_check(h);
+        REQUIRE(n_waves != nullptr, "n_waves is required");
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        // (the last launch was owned: the fused kernel over the whole epoch, in its <.., true> instantiation)
+        const bool owned = h->hog_form_used == 1 && h->own_waves > 0 && h->hog_kernel == pick_mf_kernel(h->k, true) &&
+                           h->hog_kernel != pick_mf_kernel(h->k, false);
+        *n_waves = owned ? h->own_waves : 0;
+        if (!owned) return;
+        if (wave_ptr) HIP_CHECK(hipMemcpy(wave_ptr, h->wave_ptr.p, sizeof(int64_t) * ((size_t)h->own_waves + 1), hipMemcpyDeviceToHost));
+        if (own_u) HIP_CHECK(hipMemcpy(own_u, h->own_u.p, sizeof(int32_t) * (size_t)h->nnz, hipMemcpyDeviceToHost));
+        if (own_i) HIP_CHECK(hipMemcpy(own_i, h->own_i.p, sizeof(int32_t) * (size_t)h->nnz, hipMemcpyDeviceToHost));
+    });
+}
+
 int cornac_hip_mf_last_timing(cornac_hip_mf_t h, double *ms4) {
     return guarded([&] {
         REQUIRE(h && ms4, "NULL argument");

@@ -424,6 +424,15 @@ int cornac_hip_mf_fit(cornac_hip_mf_t h, int max_iter, float lr, float reg, floa
  * 1 if the rotation gave up once (workgroup placement / barrier bound) and the handle went back to the fused kernel}. */
 int cornac_hip_mf_hogwild_form(cornac_hip_mf_t h, int form);
 int cornac_hip_mf_hogwild_stats(cornac_hip_mf_t h, int64_t *out4);
+/* Read-only test hooks of the hogwild forms; both copy from the handle's tables and change nothing.
+ * debug_split: *n_split receives the number of item rows that train through copies and *n_virtual the number of copies
+ * (0 and 0 before the first hogwild launch, or when no row is split); split_item[n_split] and split_ptr[n_split + 1]
+ * (copies of split item j = virtual rows [split_ptr[j], split_ptr[j + 1]), ids n_items + v) receive the tables when non-NULL.
+ * debug_ownership: *n_waves receives the width W of the persistent grid when the LAST hogwild launch ran the fused kernel
+ * with user-row ownership (0 otherwise); wave_ptr[W + 1], own_u[nnz] (negative = shared heavy user, stored as ~u) and
+ * own_i[nnz] (ids >= n_items name copies of split rows) receive the tables when non-NULL. */
+int cornac_hip_mf_debug_split(cornac_hip_mf_t h, int64_t *n_split, int64_t *n_virtual, int32_t *split_item, int32_t *split_ptr);
+int cornac_hip_mf_debug_ownership(cornac_hip_mf_t h, int64_t *n_waves, int64_t *wave_ptr, int32_t *own_u, int32_t *own_i);
 /* One-shot form with the reference's exact argument list (host buffers, in place). */
 int cornac_hip_mf_fit_sgd(int device, const int64_t *rid, const int64_t *cid, const float *val, int64_t nnz, float *U,
                           float *V, float *Bu, float *Bi, int64_t n_users, int64_t n_items, int k, float lr, float reg,

@@ -955,6 +955,66 @@ void oracle_bpr_jacobi_f64(const int64_t *u, const int64_t *i, const int64_t *j,
     }
 }
 
+/* The MF update of a list of ratings in float64, one after another in `order` (oracle/mf_step_oracle.py `sequential`): all
+ * four deltas of a rating come from the values before it, as the hogwild MF kernels compute them. */
+void oracle_mf_apply_seq_f64(const int64_t *u, const int64_t *i, const float *r, const int64_t *order, int64_t n, double *U,
+                             double *V, double *Bu, double *Bi, int k, double lr, double reg, double mu, int use_bias) {
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t s = order[t];
+        double *pu = U + u[s] * k, *pi = V + i[s] * k;
+        double dot = 0;
+        for (int f = 0; f < k; ++f) dot += pu[f] * pi[f];
+        const double err = (double)r[s] - (mu + Bu[u[s]] + Bi[i[s]] + dot);
+        for (int f = 0; f < k; ++f) {
+            const double uf = pu[f], vf = pi[f];
+            pu[f] = uf + lr * (err * vf - reg * uf);
+            pi[f] = vf + lr * (err * uf - reg * vf);
+        }
+        if (use_bias) {
+            Bu[u[s]] += lr * (err - reg * Bu[u[s]]);
+            Bi[i[s]] += lr * (err - reg * Bi[i[s]]);
+        }
+    }
+}
+
+/* The same deltas, every rating's from the float32 START tables, summed per row in float64 (`jacobi` there): sums, touch
+ * counts, and the floored path of a row = sum over its ratings of lr (max(|err|, err_floor) |other row| + reg |own row|)
+ * (a bias: lr (max(|err|, err_floor) + reg |b|)).  The output arrays arrive zeroed; biases are touched only with use_bias. */
+void oracle_mf_jacobi_f64(const int64_t *u, const int64_t *i, const float *r, int64_t n, const float *U, const float *V,
+                          const float *Bu, const float *Bi, int k, double lr, double reg, double mu, int use_bias,
+                          double err_floor, double *sU, double *sV, double *sBu, double *sBi, double *pU, double *pV, double *pBu,
+                          double *pBi, int64_t *tU, int64_t *tV, int64_t *tBu, int64_t *tBi, double *err_out) {
+    for (int64_t t = 0; t < n; ++t) {
+        const float *pu = U + u[t] * k, *pi = V + i[t] * k;
+        double *su = sU + u[t] * k, *si = sV + i[t] * k;
+        const double bu = Bu[u[t]], bi = Bi[i[t]];
+        double dot = 0, nu2 = 0, ni2 = 0;
+        for (int f = 0; f < k; ++f) {
+            dot += (double)pu[f] * (double)pi[f];
+            nu2 += (double)pu[f] * (double)pu[f];
+            ni2 += (double)pi[f] * (double)pi[f];
+        }
+        const double err = (double)r[t] - (mu + bu + bi + dot);
+        for (int f = 0; f < k; ++f) {
+            const double uf = pu[f], vf = pi[f];
+            su[f] += lr * (err * vf - reg * uf);
+            si[f] += lr * (err * uf - reg * vf);
+        }
+        const double e = fabs(err) > err_floor ? fabs(err) : err_floor, nu = sqrt(nu2), ni = sqrt(ni2);
+        pU[u[t]] += lr * (e * ni + reg * nu);
+        pV[i[t]] += lr * (e * nu + reg * ni);
+        ++tU[u[t]]; ++tV[i[t]];
+        if (use_bias) {
+            sBu[u[t]] += lr * (err - reg * bu);
+            sBi[i[t]] += lr * (err - reg * bi);
+            pBu[u[t]] += lr * (e + reg * fabs(bu));
+            pBi[i[t]] += lr * (e + reg * fabs(bi));
+            ++tBu[u[t]]; ++tBi[i[t]];
+        }
+        err_out[t] = err;
+    }
+}
+
 int oracle_num_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

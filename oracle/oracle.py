@@ -127,6 +127,12 @@ def _bind(L):
         L.oracle_bpr_jacobi_f64.argtypes = [i64p, i64p, i64p, C.c_int64, f32p, f32p, f32p, C.c_int, C.c_double, C.c_double,
                                             C.c_int] + [f64p_] * 6 + [i64p] * 3 + [f64p_] * 2
         L.oracle_bpr_jacobi_f64.restype = None
+        L.oracle_mf_apply_seq_f64.argtypes = [i64p, i64p, f32p, i64p, C.c_int64, f64p_, f64p_, f64p_, f64p_, C.c_int, C.c_double,
+                                              C.c_double, C.c_double, C.c_int]
+        L.oracle_mf_apply_seq_f64.restype = None
+        L.oracle_mf_jacobi_f64.argtypes = [i64p, i64p, f32p, C.c_int64, f32p, f32p, f32p, f32p, C.c_int, C.c_double, C.c_double,
+                                           C.c_double, C.c_int, C.c_double] + [f64p_] * 8 + [i64p] * 4 + [f64p_]
+        L.oracle_mf_jacobi_f64.restype = None
         L.oracle_num_threads.restype = C.c_int
         L.oracle_sizeof_mt.restype = C.c_int
     return L
@@ -596,6 +602,33 @@ def bpr_jacobi_f64(trip, tables, lr, reg, use_bias):
     lib().oracle_bpr_jacobi_f64(u, i, j, len(u), U, V, B, U.shape[1], float(lr), float(reg), int(bool(use_bias)),
                                 *[out[tab]["sum"] for tab in "UVB"], *[out[tab]["path"] for tab in "UVB"],
                                 *[out[tab]["touches"] for tab in "UVB"], out["x"], out["z"])
+    return out
+
+
+MF_TABLES = ("U", "V", "Bu", "Bi")
+
+
+def mf_apply_seq_f64(rat, order, U, V, Bu, Bi, lr, reg, mu, use_bias):
+    """float64 tables (modified in place) after the ratings' updates, one after another in `order`"""
+    u, i = (np.ascontiguousarray(a, np.int64) for a in rat[:2])
+    r, order = np.ascontiguousarray(rat[2], np.float32), np.ascontiguousarray(order, np.int64)
+    assert U.dtype == V.dtype == Bu.dtype == Bi.dtype == np.float64 and len(order) <= len(u)
+    lib().oracle_mf_apply_seq_f64(u, i, r, order, len(order), U, V, Bu, Bi, U.shape[1], float(lr), float(reg), float(mu),
+                                  int(bool(use_bias)))
+
+
+def mf_jacobi_f64(rat, tables, lr, reg, mu, use_bias, err_floor):
+    """every rating's deltas from the float32 start tables, summed per row in float64: {"U" | "V" | "Bu" | "Bi": dict(sum,
+    touches, path), "err"} (oracle/mf_step_oracle.py `jacobi`)"""
+    u, i = (np.ascontiguousarray(a, np.int64) for a in rat[:2])
+    r = np.ascontiguousarray(rat[2], np.float32)
+    tabs = [np.ascontiguousarray(t, np.float32) for t in tables]
+    out = {tab: dict(sum=np.zeros(t.shape), touches=np.zeros(len(t), np.int64), path=np.zeros(len(t)))
+           for tab, t in zip(MF_TABLES, tabs)}
+    out["err"] = np.empty(len(u))
+    lib().oracle_mf_jacobi_f64(u, i, r, len(u), *tabs, tabs[0].shape[1], float(lr), float(reg), float(mu), int(bool(use_bias)),
+                               float(err_floor), *[out[tab]["sum"] for tab in MF_TABLES], *[out[tab]["path"] for tab in MF_TABLES],
+                               *[out[tab]["touches"] for tab in MF_TABLES], out["err"])
     return out
 
 
