@@ -41,6 +41,7 @@ SYMBOLS = [
     "cornac_hip_bpr_last_timing", "cornac_hip_bpr_kernel_timing", "cornac_hip_mf_kernel_timing",
     "cornac_hip_bpr_debug_ownership", "cornac_hip_bpr_set_views", "cornac_hip_bpr_seed_view_stream",
     "cornac_hip_vebpr_fit_epochs", "cornac_hip_vebpr_fit_epochs_f64", "cornac_hip_vebpr_hogwild_form",
+    "cornac_hip_mmmf_fit_epochs", "cornac_hip_mmmf_fit_epochs_f64", "cornac_hip_mmmf_hogwild_enqueue",
     "cornac_hip_bpr_strata_config", "cornac_hip_bpr_chunk_records", "cornac_hip_bpr_strata_stats", "cornac_hip_bpr_debug_strata",
     "cornac_hip_bpr_ldsbin_config", "cornac_hip_bpr_ldsbin_pass_config", "cornac_hip_bpr_ldsbin_stats",
     "cornac_hip_bpr_ldsbin_deal_config", "cornac_hip_bpr_debug_ldsbin_deal",
@@ -173,6 +174,11 @@ def lib():
                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.cornac_hip_vebpr_fit_epochs_f64.argtypes = [_vp, C.c_int, C.c_double, C.c_double, C.c_double,
                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.cornac_hip_mmmf_fit_epochs.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_int64)]
+        L.cornac_hip_mmmf_fit_epochs_f64.argtypes = [_vp, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int64),
+                                                     C.POINTER(C.c_int64)]
+        L.cornac_hip_mmmf_hogwild_enqueue.argtypes = [_vp, C.c_int64, C.c_float, C.c_float]
         L.cornac_hip_bpr_sample_triplets.argtypes = [_vp, C.c_int64, C.c_int, _vp, _vp, _vp]
         L.cornac_hip_bpr_apply_triplets.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_float,
                                                     C.c_float, C.c_int]
@@ -583,6 +589,22 @@ class BprTrainer:
         o = C.c_int()
         check(lib().cornac_hip_vebpr_hogwild_form(self.h, C.byref(o)))
         return bool(o.value)
+
+    def mmmf_fit_epochs(self, n_epochs, lr, reg, mode=MODE_HOGWILD):
+        """MMMF's hinge loss on this handle (recom_mmmf.pyx:126-158): (correct, skipped) summed over the call"""
+        c, s = C.c_int64(), C.c_int64()
+        check(lib().cornac_hip_mmmf_fit_epochs(self.h, n_epochs, lr, reg, mode, C.byref(c), C.byref(s)))
+        return c.value, s.value
+
+    def mmmf_fit_epochs_f64(self, n_epochs, lr, reg):
+        """float64 tables (set_factors_f64): sequential semantics, everything in double (recom_mmmf.pyx:103-116)"""
+        c, s = C.c_int64(), C.c_int64()
+        check(lib().cornac_hip_mmmf_fit_epochs_f64(self.h, n_epochs, float(lr), float(reg), C.byref(c), C.byref(s)))
+        return c.value, s.value
+
+    def mmmf_hogwild_enqueue(self, n_samples, lr, reg):
+        """one MMMF hogwild launch at the current sample offset; sync() collects the counters"""
+        check(lib().cornac_hip_mmmf_hogwild_enqueue(self.h, n_samples, lr, reg))
 
     def debug_ownership(self):
         """(wave_ptr, own_u, own_i) of the hogwild sampler's user-row ownership, or None if unused"""

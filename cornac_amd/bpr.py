@@ -1,4 +1,4 @@
-"""BPR and WBPR on MI355X — same constructor, `fit/score/rank` surface and learned attributes
+"""BPR, WBPR and MMMF on MI355X — same constructor, `fit/score/rank` surface and learned attributes
 (`u_factors`, `i_factors`, `i_biases`) as the reference models
 (cornac/models/bpr/recom_bpr.pyx:65-333, cornac/models/bpr/recom_wbpr.pyx:30-144); the per-epoch
 `_fit_sgd` call is replaced by libcornac_hip (include/cornac_hip.h).
@@ -39,6 +39,7 @@ class BPR(Recommender):
 
     _neg_population = _lib.NEG_UNIFORM
     _shared_stream = False
+    _pairwise_loss = "bpr"  # what the multi-GPU trainers of dist.py run; a subclass with another loss names it
 
     def __init__(self, name="BPR", k=10, max_iter=100, learning_rate=0.001, lambda_reg=0.01, use_bias=True,
                  num_threads=0, trainable=True, verbose=False, init_params=None, seed=None, mode=None, device=0):
@@ -96,6 +97,12 @@ class BPR(Recommender):
             lo, hi = int(self.rng.randint(2 ** 31)), int(self.rng.randint(2 ** 31))
             trainer.seed_hogwild((hi << 32) | lo)
 
+    def _run_epochs(self, trainer, n, f64, mode):
+        """n epochs of this model's loss on the trainer -> (correct, skipped) summed over them"""
+        if f64:
+            return trainer.fit_epochs_f64(n, self.learning_rate, self.lambda_reg, self.use_bias, self._neg_population)
+        return trainer.fit_epochs(n, self.learning_rate, self.lambda_reg, self.use_bias, self._neg_population, mode)
+
     def fit(self, train_set, val_set=None):
         Recommender.fit(self, train_set, val_set)
         self._init()
@@ -121,9 +128,7 @@ class BPR(Recommender):
             self.fit_stats = []
 
             def run(n):
-                if f64:
-                    return trainer.fit_epochs_f64(n, self.learning_rate, self.lambda_reg, self.use_bias, self._neg_population)
-                return trainer.fit_epochs(n, self.learning_rate, self.lambda_reg, self.use_bias, self._neg_population, mode)
+                return self._run_epochs(trainer, n, f64, mode)
 
             if self.verbose:
                 from tqdm.auto import trange
@@ -200,6 +205,27 @@ class WBPR(BPR):
         else:
             lo, hi = int(self.rng.randint(2 ** 31)), int(self.rng.randint(2 ** 31))
             trainer.seed_hogwild((hi << 32) | lo)
+
+
+class MMMF(BPR):
+    """Maximum Margin Matrix Factorization (Weimer et al., Machine Learning 2008): BPR's sampler and tables under the
+    soft-margin (hinge) ranking loss — constructor and `fit/score/rank` surface of
+    cornac/models/mmmf/recom_mmmf.pyx:33-98, plus `mode` and `device` as for BPR.  A sampled triplet whose score is
+    already positive updates nothing; a violator takes a step that does not depend on the score, its two biases always
+    included (recom_mmmf.pyx:145-158).  There is no `use_bias` argument: BPR's default (True) is inherited."""
+
+    _pairwise_loss = "hinge"
+
+    def __init__(self, name="MMMF", k=10, max_iter=100, learning_rate=0.001, lambda_reg=0.01, num_threads=0,
+                 trainable=True, verbose=False, init_params=None, seed=None, mode=None, device=0):
+        super().__init__(name=name, k=k, max_iter=max_iter, learning_rate=learning_rate, lambda_reg=lambda_reg,
+                         num_threads=num_threads, trainable=trainable, verbose=verbose, init_params=init_params,
+                         seed=seed, mode=mode, device=device)
+
+    def _run_epochs(self, trainer, n, f64, mode):
+        if f64:
+            return trainer.mmmf_fit_epochs_f64(n, self.learning_rate, self.lambda_reg)
+        return trainer.mmmf_fit_epochs(n, self.learning_rate, self.lambda_reg, mode)
 
 
 class VEBPR(Recommender):

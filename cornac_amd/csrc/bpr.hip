@@ -1072,7 +1072,25 @@ static void launch_det_level(cornac_hip_bpr_t h, const int32_t *ou, const int32_
                            h->U.p, h->V.p, h->B.p, h->k, (float)lr, (float)reg, use_bias, h->counters.p);
 }
 
-static void bpr_epoch_deterministic(cornac_hip_bpr_t h, double lr, double reg, int use_bias, int neg_population) {
+// one level of the schedule, launched with the lane-group width G = pow2_group(k)
+typedef void (*DetLevelLaunch)(cornac_hip_bpr_t h, int G, const int32_t *ou, const int32_t *oi, const int32_t *oj, int64_t off,
+                               int cnt, double lr, double reg, int use_bias);
+
+static void bpr_det_level_launch(cornac_hip_bpr_t h, int G, const int32_t *ou, const int32_t *oi, const int32_t *oj,
+                                 int64_t off, int cnt, double lr, double reg, int use_bias) {
+    switch (G) {
+        case 4: launch_det_level<4>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
+        case 8: launch_det_level<8>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
+        case 16: launch_det_level<16>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
+        case 32: launch_det_level<32>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
+        default: launch_det_level<64>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
+    }
+}
+
+// `level` selects the loss: the sampling, the level builder and the bucketing are the same for every pairwise loss on this
+// handle, only the kernel of a level differs (BPR's log-sigmoid here, MMMF's hinge in mmmf.inc)
+static void bpr_epoch_deterministic(cornac_hip_bpr_t h, double lr, double reg, int use_bias, int neg_population,
+                                    DetLevelLaunch level = bpr_det_level_launch) {
     REQUIRE(h->mt_seeded, "deterministic mode needs cornac_hip_bpr_seed_mt19937 first");
     // (the sequential engine restates recom_wbpr.pyx:131-139, whose negatives are the items of THIS matrix's interactions; a
     // caller-supplied population — the multi-GPU driver's global popularity — belongs to the hogwild forms)
@@ -1145,13 +1163,7 @@ static void bpr_epoch_deterministic(cornac_hip_bpr_t h, double lr, double reg, i
             const int64_t off = lp[l];
             const int cnt = (int)(lp[l + 1] - lp[l]);
             if (cnt <= 0) continue;
-            switch (G) {
-                case 4: launch_det_level<4>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
-                case 8: launch_det_level<8>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
-                case 16: launch_det_level<16>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
-                case 32: launch_det_level<32>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
-                default: launch_det_level<64>(h, ou, oi, oj, off, cnt, lr, reg, use_bias); break;
-            }
+            level(h, G, ou, oi, oj, off, cnt, lr, reg, use_bias);
         }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -2697,3 +2709,4 @@ int cornac_hip_bpr_last_timing(cornac_hip_bpr_t h, double *ms4) {
 
 #include "vebpr.inc"
 #include "sharded.inc"
+#include "mmmf.inc"

@@ -1942,6 +1942,15 @@ def global_negative_population(indices_local, n_items, device=None, group=None, 
     return population_from_degrees(global_item_degrees(indices_local, n_items, device, group), at_most)
 
 
+def _require_bpr_loss(model):
+    """The multi-GPU BPR trainers run BPR's log-sigmoid loss and read only `_neg_population` off the model: a model whose
+    class names another pairwise loss (`_pairwise_loss`, e.g. MMMF's hinge) would silently be trained with the wrong one."""
+    loss = getattr(type(model), "_pairwise_loss", "bpr")
+    if loss != "bpr":
+        raise TypeError("%s trains the %r loss; the sharded / ring BPR trainers only have BPR's: fit it on one device "
+                        "with model.fit(train_set)" % (type(model).__name__, loss))
+
+
 def fit_bpr_sharded(model, train_set, device=None, group=None, sync_per_epoch=None, sparse_threshold=None,
                     trainer_factory=None, local_popularity=False, rule=None, regime="auto", rings=1):
     """`model.fit(train_set)` for a cornac_amd BPR / WBPR over all ranks of the process group (regime 1).  Every rank
@@ -1965,6 +1974,7 @@ def fit_bpr_sharded(model, train_set, device=None, group=None, sync_per_epoch=No
     from . import _lib
     from .recommender import Recommender
 
+    _require_bpr_loss(model)
     if regime not in ("auto", "replicated", "ring"):
         raise ValueError("regime must be 'auto', 'replicated' or 'ring'")
     if model.effective_mode != "hogwild":
@@ -2068,6 +2078,7 @@ def fit_bpr_ring(model, train_set, device=None, group=None, trainer_factory=None
     from . import _lib
     from .recommender import Recommender
 
+    _require_bpr_loss(model)
     if model.effective_mode != "hogwild":
         raise ValueError("sequential (seeded, mode=None) semantics do not shard: build the model with mode='hogwild'")
     world, rank = _world(group)

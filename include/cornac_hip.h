@@ -392,6 +392,35 @@ int cornac_hip_vebpr_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr,
 int cornac_hip_vebpr_hogwild_form(cornac_hip_bpr_t h, int *owned);
 
 /* ------------------------------------------------------------------------- *
+ * MMMF (maximum-margin matrix factorisation) on the same handle.
+ * Replaces: MMMF._fit_sgd(rng_pos, rng_neg, ..., U, V, B)
+ *           cornac/models/mmmf/recom_mmmf.pyx:103-160 under BPR's caller loop
+ *           (cornac/models/bpr/recom_bpr.pyx:189-206).
+ * BPR's sampler under the soft-margin ranking loss: a triplet whose score is
+ * already positive is counted in `correct` and updates nothing (:145-147); a
+ * violator (score <= 0) moves its three rows and, always, its two biases
+ * (:150-158; the loop has no use_bias switch).  Uniform negatives only.
+ * Every entry point refuses, with an error code and a cornac_hip_last_error
+ * text: a handle with a negative population set, a conveyor-configured handle,
+ * the table type the call is not for, n_epochs < 0, an unknown mode, and a mode
+ * whose sampler has not been seeded.
+ * ------------------------------------------------------------------------- */
+/* n_epochs epochs of recom_mmmf.pyx:126-158 over float32 tables; mode: CORNAC_HIP_MODE_DETERMINISTIC (after
+ * cornac_hip_bpr_seed_mt19937: the two mt19937 streams, sequential semantics, bit-faithful) or CORNAC_HIP_MODE_HOGWILD
+ * (after cornac_hip_bpr_seed_hogwild: the reference's num_threads > 1 prange, :123-126).  correct / skipped are summed
+ * over the call, as in cornac_hip_bpr_fit_epochs. */
+int cornac_hip_mmmf_fit_epochs(cornac_hip_bpr_t h, int n_epochs, float lr, float reg, int mode, int64_t *correct,
+                               int64_t *skipped);
+/* The float64 instantiation of the same fused-type function (recom_mmmf.pyx:103-106 `floating[:, :] U, ... floating[:] B`,
+ * locals :113-116), reached by float64 init_params: tables set with cornac_hip_bpr_set_factors_f64, sequential semantics
+ * only, like cornac_hip_bpr_fit_epochs_f64. */
+int cornac_hip_mmmf_fit_epochs_f64(cornac_hip_bpr_t h, int n_epochs, double lr, double reg, int64_t *correct,
+                                   int64_t *skipped);
+/* One hogwild launch of n_samples iterations of recom_mmmf.pyx:126-158 at the handle's current sample offset (the
+ * numbering of BPR's unowned fused form), asynchronous; cornac_hip_bpr_sync collects the counters. */
+int cornac_hip_mmmf_hogwild_enqueue(cornac_hip_bpr_t h, int64_t n_samples, float lr, float reg);
+
+/* ------------------------------------------------------------------------- *
  * Matrix factorisation trainer.
  * Replaces: backend_cpu.fit_sgd(rid, cid, val, U, V, Bu, Bi, lr, reg, mu,
  *           max_iter, num_threads, use_bias, early_stop, verbose)
