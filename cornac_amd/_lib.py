@@ -64,6 +64,8 @@ SYMBOLS = [
     "cornac_hip_mf_fit_minibatch", "cornac_hip_mf_fit_minibatch_dropout", "cornac_hip_mf_reset_optimizer",
     "cornac_hip_mf_pmf_set_factors", "cornac_hip_mf_pmf_get_factors", "cornac_hip_mf_pmf_fit", "cornac_hip_mf_pmf_form",
     "cornac_hip_mf_nmf_set_factors", "cornac_hip_mf_nmf_get_factors", "cornac_hip_mf_nmf_fit", "cornac_hip_mf_nmf_form",
+    "cornac_hip_mf_hpf_set_tables", "cornac_hip_mf_hpf_get_tables", "cornac_hip_mf_hpf_fit", "cornac_hip_mf_hpf_elog",
+    "cornac_hip_mf_hpf_form",
     "cornac_hip_scorer_create", "cornac_hip_scorer_destroy", "cornac_hip_scorer_set", "cornac_hip_score_user",
     "cornac_hip_scorer_set_f64", "cornac_hip_score_user_f64",
     "cornac_hip_score_block", "cornac_hip_rank_topk", "cornac_hip_rank_topk_device", "cornac_hip_score_pairs",
@@ -237,6 +239,11 @@ def lib():
         L.cornac_hip_mf_nmf_get_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
         L.cornac_hip_mf_nmf_fit.argtypes = [_vp, C.c_int] + [C.c_float] * 6 + [C.c_int, C.c_int, _vp]
         L.cornac_hip_mf_nmf_form.argtypes = [_vp] + [C.POINTER(C.c_int)] * 3
+        L.cornac_hip_mf_hpf_set_tables.argtypes = [_vp] * 5
+        L.cornac_hip_mf_hpf_get_tables.argtypes = [_vp] * 7
+        L.cornac_hip_mf_hpf_fit.argtypes = [_vp, C.c_int, C.c_int]
+        L.cornac_hip_mf_hpf_elog.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_mf_hpf_form.argtypes = [_vp] + [C.POINTER(C.c_int)] * 2
         L.cornac_hip_wmf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, C.c_int, _i64, _i32, _f32,
                                             C.c_int64]
         L.cornac_hip_wmf_destroy.argtypes = [_vp]
@@ -843,6 +850,46 @@ class MfTrainer:
         1 dataflow launch / 2 level schedule; rows summed in more than one piece"""
         o = [C.c_int(), C.c_int(), C.c_int()]
         check(lib().cornac_hip_mf_nmf_form(self.h, *[C.byref(x) for x in o]))
+        return tuple(x.value for x in o)
+
+    # ---- HPF on the same handle (float64 shape / rate tables of its own; the ratings must be stored by user) ----------
+    HPF_MAX_K = 256
+
+    def hpf_set_tables(self, G_s, G_r, L_s, L_r):
+        """float64 G_s, G_r [n_users, k], L_s, L_r [n_items, k]: strictly positive and finite, k <= 256"""
+        nu, ni, k = self.shape
+        if k > self.HPF_MAX_K:
+            raise ValueError("HPF keeps a row's sums in registers: k = %d is above its limit of %d" % (k, self.HPF_MAX_K))
+        tables = [np.ascontiguousarray(a, np.float64) for a in (G_s, G_r, L_s, L_r)]
+        for a, name, shape in zip(tables, ("G_s", "G_r", "L_s", "L_r"), ((nu, k), (nu, k), (ni, k), (ni, k))):
+            if a.shape != shape:
+                raise ValueError("HPF table %s must be %r, got %r" % (name, shape, a.shape))
+            if not (np.isfinite(a).all() and (a > 0).all()):
+                raise ValueError("HPF table %s must be strictly positive and finite" % name)
+        check(lib().cornac_hip_mf_hpf_set_tables(self.h, *[a.ctypes.data for a in tables]))
+
+    def hpf_get_tables(self):
+        """(G_s, G_r, L_s, L_r, K_r, T_r)"""
+        nu, ni, k = self.shape
+        out = [np.empty(s, np.float64) for s in ((nu, k), (nu, k), (ni, k), (ni, k), (nu,), (ni,))]
+        check(lib().cornac_hip_mf_hpf_get_tables(self.h, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def hpf_fit(self, n_iters, hierarchical=True):
+        """n_iters variational iterations from the stored tables; K_r / T_r restart as in the reference's routine"""
+        check(lib().cornac_hip_mf_hpf_fit(self.h, int(n_iters), int(bool(hierarchical))))
+
+    def hpf_elog(self):
+        """(Lt, Lb) = exp(digamma(shape) - log rate) of the current tables"""
+        nu, ni, k = self.shape
+        Lt, Lb = np.empty((nu, k), np.float64), np.empty((ni, k), np.float64)
+        check(lib().cornac_hip_mf_hpf_elog(self.h, Lt.ctypes.data, Lb.ctypes.data))
+        return Lt, Lb
+
+    def hpf_form(self):
+        """(group, rows_split) of the last HPF iteration: lanes per row (0: none yet), rows summed in more than one piece"""
+        o = [C.c_int(), C.c_int()]
+        check(lib().cornac_hip_mf_hpf_form(self.h, *[C.byref(x) for x in o]))
         return tuple(x.value for x in o)
 
     def kernel_timing(self, enable=True):

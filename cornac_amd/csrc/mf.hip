@@ -435,6 +435,7 @@ struct NmfPlan {
     bool built = false;
     NmfSide side[2];      // users (CSR), items (CSC)
     DevBuf<float> part;   // partial sums of split rows: [slot][2][k]
+    int32_t n_slots = 0;  // slots of both sides (hpf.inc sizes its own float64 partials by it)
     int rows_split = 0;
 };
 
@@ -514,6 +515,11 @@ struct cornac_hip_mf {
     DevBuf<int32_t> nmf_c_row_id;
     DevBuf<unsigned int> nmf_ver, nmf_abort;
     int nmf_sum_form = 0, nmf_bias_form = 0, nmf_rows_split = 0;  // last epoch (cornac_hip_mf_nmf_form)
+    // HPF (hpf.inc): float64 shape / rate tables of its own, the two expected-log tables, the ratio column sums and their
+    // per-block partials, the partial sums of split rows; NMF's CSR / CSC views and its split plan are shared
+    DevBuf<double> hpf_Gs, hpf_Gr, hpf_Ls, hpf_Lr, hpf_Kr, hpf_Tr, hpf_Lt, hpf_Lb, hpf_col, hpf_colpart, hpf_part, hpf_dk;
+    bool hpf_set = false;
+    int hpf_group = 0, hpf_rows_split = 0;  // last iteration (cornac_hip_mf_hpf_form)
 };
 
 #include "mf_blocks.inc"
@@ -1556,3 +1562,4 @@ int cornac_hip_mf_last_timing(cornac_hip_mf_t h, double *ms4) {
 #include "mf_minibatch.inc"
 #include "pmf.inc"
 #include "nmf.inc"
+#include "hpf.inc"

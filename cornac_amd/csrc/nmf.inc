@@ -498,6 +498,7 @@ static void nmf_build_plan(cornac_hip_mf_t h, int mode) {
     nmf_build_segments(h, pl.side[0], h->nmf_uptr_h, split, 0, &slots);
     nmf_build_segments(h, pl.side[1], h->nmf_iptr_h, split, slots, &slots);
     pl.part.alloc(std::max<size_t>((size_t)slots * 2 * h->k, 1));
+    pl.n_slots = slots;
     pl.rows_split = (int)(pl.side[0].n_comb + pl.side[1].n_comb);
     HIP_CHECK(hipStreamSynchronize(h->stream));
     pl.built = true;

@@ -537,6 +537,37 @@ int cornac_hip_mf_nmf_fit(cornac_hip_mf_t h, int n_epochs, float lr, float lambd
  * 2 level schedule (the prange body's bias lines, :236-238); *rows_split rows summed in more than one piece */
 int cornac_hip_mf_nmf_form(cornac_hip_mf_t h, int *sum_form, int *bias_form, int *rows_split);
 
+/* HPF on the same handle: Poisson factorisation's variational updates in float64, tables of their own (the MF, PMF and NMF
+ * state of the handle is untouched, and their fits leave these alone).
+ * Replaces: hpf_cpp(tX, k, G_s, G_r, L_s, L_r, K_r, T_r, maxiter)   cornac/models/hpf/cpp/cpp_hpf.cpp:208-275
+ *           pf_cpp (the same arguments)                              cornac/models/hpf/cpp/cpp_hpf.cpp:139-203
+ *           as hpf.hpf / hpf.pf call them (cornac/models/hpf/cython/hpf.pyx:100-164 / :35-97).
+ * The handle's ratings must be stored by user (rid non-decreasing), as for NMF: cornac_hip_mf_hpf_fit refuses any other
+ * order.  One iteration (prior = 0.3, eps = 2^-52, k_s = t_s = 0.3 (1 + k) hierarchical / 0.3 otherwise):
+ *   Lt = exp(digamma(G_s) - log G_r), Lb = exp(digamma(L_s) - log L_r)                       (cpp_hpf.cpp:102-123, :240-244)
+ *   G_s[u,f] = prior + sum over u's ratings of Lt[u,f] Lb[i,f] x / (eps + sum_f Lt[u,f] Lb[i,f])         (cpp_hpf.cpp:41-61)
+ *   G_r[u,f] = k_s / K_r[u] + sum_j L_s[j,f] / L_r[j,f], from the L of the iteration before              (cpp_hpf.cpp:22-37)
+ *   hierarchical: K_r[u] = 0.3 + sum_f G_s[u,f] / G_r[u,f]                                               (cpp_hpf.cpp:7-19)
+ *   L_s, L_r, T_r likewise by item, from the same Lt and Lb and from the new G                           (cpp_hpf.cpp:65-84)
+ * Every table must be strictly positive and finite (the caller checks): the reference's detour through pruned sparse
+ * matrices is this dense formula then, and its treatment of zeros is not reproduced.
+ * One mode.  Every sum takes a fixed order of its own (rows longer than 256 ratings in pieces added in ascending order,
+ * the column sums as trees): the same bits run to run, one owner per accumulator row, no float atomics.  The reference's
+ * own order cannot be held bit for bit (digamma, log and exp are other implementations); results are compared with a
+ * tolerance.  k <= 256: a row's sums live in registers. */
+/* float64 G_s, G_r [n_users,k], L_s, L_r [n_items,k], all required; k > 256: CORNAC_HIP_ERR_INVALID */
+int cornac_hip_mf_hpf_set_tables(cornac_hip_mf_t h, const double *G_s, const double *G_r, const double *L_s, const double *L_r);
+/* any pointer may be NULL; K_r [n_users], T_r [n_items] as the last fit left them */
+int cornac_hip_mf_hpf_get_tables(cornac_hip_mf_t h, double *G_s, double *G_r, double *L_s, double *L_r, double *K_r, double *T_r);
+/* n_iters iterations of cpp_hpf.cpp:238-273 (hierarchical != 0) or :166-201.  As there, K_r = T_r = 1 at the start of every
+ * call (hpf.pyx:148-149) and, hierarchical, are then computed from the tables (cpp_hpf.cpp:231-234): 1 + 2 iterations
+ * over two calls give the bits of 3 */
+int cornac_hip_mf_hpf_fit(cornac_hip_mf_t h, int n_iters, int hierarchical);
+/* the expected-log step alone on the current tables (cpp_hpf.cpp:240-244): Lt [n_users,k], Lb [n_items,k], either may be NULL */
+int cornac_hip_mf_hpf_elog(cornac_hip_mf_t h, double *Lt, double *Lb);
+/* the last iteration (0 = none yet): *group lanes per row, *rows_split rows summed in more than one piece */
+int cornac_hip_mf_hpf_form(cornac_hip_mf_t h, int *group, int *rows_split);
+
 /* Minibatch path with dense optimisers on the same handle.
  * Replaces: backend_pt.learn(model, train_set, n_epochs, batch_size, learning_rate, reg, optimizer)
  *           cornac/models/mf/backend_pt.py:67-106 and the forward of backend_pt.MF (:56-65), selected by
