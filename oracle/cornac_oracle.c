@@ -1015,6 +1015,138 @@ void oracle_mf_jacobi_f64(const int64_t *u, const int64_t *i, const float *r, in
     }
 }
 
+/* Hogwild VEBPR (csrc/vebpr.inc vebpr_hogwild_kernel): its sampler restated.  Unowned form: counter = (sample_lo,
+ * sample_hi, epoch, 2), positive = Lemire draw of words (0, 1) over the n_pos interactions.  Both forms: word 2 is the
+ * view word (the caller turns it into a position of the user's view row: (w2 * nv) >> 32) and the negative is the plain
+ * multiply-shift (w3 * n_items) >> 32 — no Lemire rejection on either. */
+void oracle_vebpr_hogwild_sample(uint64_t seed, uint32_t epoch, int64_t s0, int64_t n, uint32_t n_pos, uint32_t n_items,
+                                 int64_t *ii_out, uint32_t *w2_out, int64_t *jj_out) {
+    for (int64_t t = 0; t < n; ++t) {
+        uint64_t s = (uint64_t)(s0 + t);
+        uint32_t w[4];
+        oracle_philox4x32((uint32_t)s, (uint32_t)(s >> 32), epoch, 2u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+        ii_out[t] = lemire_bounded2(w[0], w[1], n_pos);
+        w2_out[t] = w[2];
+        jj_out[t] = (int64_t)(((uint64_t)w[3] * n_items) >> 32);
+    }
+}
+
+/* Owned form: wave `wave_id` draws its local samples [lo, hi) from its own slice of length `len`; counter = (local,
+ * wave_id, epoch, 3). */
+void oracle_vebpr_hogwild_sample_owned(uint64_t seed, uint32_t epoch, uint32_t wave_id, uint32_t len, uint32_t n_items,
+                                       int64_t lo, int64_t hi, int64_t *r_out, uint32_t *w2_out, int64_t *jj_out) {
+    for (int64_t t = lo; t < hi; ++t) {
+        uint32_t w[4];
+        oracle_philox4x32((uint32_t)t, wave_id, epoch, 3u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+        r_out[t - lo] = lemire_bounded2(w[0], w[1], len);
+        w2_out[t - lo] = w[2];
+        jj_out[t - lo] = (int64_t)(((uint64_t)w[3] * n_items) >> 32);
+    }
+}
+
+/* The hogwild VEBPR update of ONE quadruple (u, i, v, j) in float64, as vebpr_hogwild_kernel states it (oracle/
+ * vebpr_step_oracle.py has the formulas): all four deltas from the rows as they are passed in.  pv == NULL: the user has
+ * no views (a clamped, bias-free BPR step; dV is not written).  x[3] = the clamped scores x_ij, x_iv, x_vj (the last two
+ * 0 without a view).  `fault` != 0 selects one of the deliberately wrong variants that vebpr_step_oracle.FAULTS names, in
+ * that order — tests/test_vebpr_step_cpu.py feeds them to the checks to prove that those would notice.  Returns 1 if dV
+ * was written (with fault 3 also without a view: the caller then lands it on row i). */
+static int vebpr_quad_f64(const double *pu, const double *pi, const double *pv, const double *pj, int k, double lr,
+                          double reg, double alpha, int fault, double *dU, double *dI, double *dV, double *dJ, double x[3]) {
+    const int has_v = pv != NULL;
+    const double *qv = has_v ? pv : pi;
+    const int kd = fault == 7 ? k - 1 : k; /* last_lane_left_out */
+    double x_ij = 0, x_iv = 0, x_vj = 0;
+    for (int f = 0; f < kd; ++f) {
+        x_ij += pu[f] * (pi[f] - pj[f]);
+        x_iv += pu[f] * (fault == 6 ? qv[f] - pi[f] : pi[f] - qv[f]); /* d_iv_from_v_minus_i */
+        x_vj += pu[f] * (qv[f] - pj[f]);
+    }
+    x_ij = clamp50d(x_ij); x_iv = clamp50d(x_iv); x_vj = clamp50d(x_vj);
+    const double d_ij = 1.0 / (1.0 + exp(x_ij));
+    const double d_iv = has_v ? 1.0 / (1.0 + exp(x_iv)) : 0.0, d_vj = has_v ? 1.0 / (1.0 + exp(x_vj)) : 0.0;
+    double al = has_v ? alpha : 0.0, be = has_v ? 1.0 - alpha : 0.0;
+    if (fault == 1) { const double t = al; al = be; be = t; } /* alpha_beta_swapped */
+    const int write_v = has_v || fault == 3; /* view_delta_without_view */
+    for (int f = 0; f < k; ++f) {
+        const double u0 = pu[f], vi = pi[f], vv = qv[f], vj = pj[f];
+        dU[f] = -lr * (-d_ij * (vi - vj) - al * d_iv * (vi - vv) - be * d_vj * (vv - vj) + reg * u0);
+        const double ui = fault == 5 ? u0 + dU[f] : u0; /* item_from_new_user */
+        dI[f] = -lr * (-d_ij * ui - al * d_iv * ui + reg * (fault == 4 ? vj : vi)); /* reg_from_other_row */
+        if (write_v) dV[f] = -lr * (al * d_iv * ui + (fault == 2 ? be : -be) * d_vj * ui + reg * vv); /* view_row_sign_of_d_vj */
+        dJ[f] = -lr * (d_ij * ui + be * d_vj * ui + reg * vj);
+    }
+    x[0] = x_ij; x[1] = has_v ? x_iv : 0.0; x[2] = has_v ? x_vj : 0.0;
+    return write_v;
+}
+
+/* A list of quadruples applied one after another in `order` (oracle/vebpr_step_oracle.py `sequential`); v < 0 = no view.
+ * With v == i both the i delta and the v delta land on the one row, as the kernel's two atomic adds do.  mark_tab = 1
+ * (U) or 2 (V), mark_row: that row's LAST update is afterwards applied once more with the factor mark_sign (-1: the
+ * update is lost, +1: doubled); mark_tab = 0: nothing. */
+void oracle_vebpr_apply_seq_f64(const int64_t *u, const int64_t *i, const int64_t *v, const int64_t *j, const int64_t *order,
+                                int64_t n, double *U, double *V, int k, double lr, double reg, double alpha, int fault,
+                                int mark_tab, int64_t mark_row, double mark_sign) {
+    double *buf = (double *)calloc((size_t)5 * k, sizeof(double));
+    double *dU = buf, *dI = buf + k, *dV = buf + 2 * k, *dJ = buf + 3 * k, *last = buf + 4 * k;
+    for (int64_t t = 0; t < n; ++t) {
+        const int64_t s = order[t];
+        double *pu = U + u[s] * k, *pi = V + i[s] * k, *pj = V + j[s] * k, *pv = v[s] >= 0 ? V + v[s] * k : NULL;
+        double x[3];
+        const int wv = vebpr_quad_f64(pu, pi, pv, pj, k, lr, reg, alpha, fault, dU, dI, dV, dJ, x);
+        double *tv = pv ? pv : pi;
+        const int64_t v_row = pv ? v[s] : i[s];
+        for (int f = 0; f < k; ++f) {
+            pu[f] += dU[f];
+            pi[f] += dI[f];
+            if (wv) tv[f] += dV[f];
+            pj[f] += dJ[f];
+        }
+        if (mark_tab == 1 && u[s] == mark_row) memcpy(last, dU, sizeof(double) * k);
+        if (mark_tab == 2) {
+            if (i[s] == mark_row) memcpy(last, dI, sizeof(double) * k);
+            if (wv && v_row == mark_row) memcpy(last, dV, sizeof(double) * k);
+            if (j[s] == mark_row) memcpy(last, dJ, sizeof(double) * k);
+        }
+    }
+    if (mark_tab == 1 || mark_tab == 2) {
+        double *row = (mark_tab == 1 ? U : V) + mark_row * k;
+        for (int f = 0; f < k; ++f) row[f] += mark_sign * last[f];
+    }
+    free(buf);
+}
+
+/* The same deltas, every quadruple's from the float32 START tables, summed per row in float64 (`jacobi` there): sums,
+ * touch counts (one per delta that lands on the row: a quadruple with v == i touches that row twice) and path lengths
+ * (sum of the Euclidean norms of those deltas); x_out[3 n] = the three clamped scores of every quadruple.  The output
+ * arrays arrive zeroed. */
+void oracle_vebpr_jacobi_f64(const int64_t *u, const int64_t *i, const int64_t *v, const int64_t *j, int64_t n, const float *U,
+                             const float *V, int k, double lr, double reg, double alpha, double *sU, double *sV, double *pU,
+                             double *pV, int64_t *tU, int64_t *tV, double *x_out) {
+    double *buf = (double *)calloc((size_t)8 * k, sizeof(double));
+    double *ru = buf, *ri = buf + k, *rv = buf + 2 * k, *rj = buf + 3 * k;
+    double *dU = buf + 4 * k, *dI = buf + 5 * k, *dV = buf + 6 * k, *dJ = buf + 7 * k;
+    for (int64_t t = 0; t < n; ++t) {
+        const int has_v = v[t] >= 0;
+        for (int f = 0; f < k; ++f) {
+            ru[f] = U[u[t] * k + f];
+            ri[f] = V[i[t] * k + f];
+            rj[f] = V[j[t] * k + f];
+            if (has_v) rv[f] = V[v[t] * k + f];
+        }
+        vebpr_quad_f64(ru, ri, has_v ? rv : NULL, rj, k, lr, reg, alpha, 0, dU, dI, dV, dJ, x_out + 3 * t);
+        double nu2 = 0, ni2 = 0, nv2 = 0, nj2 = 0;
+        for (int f = 0; f < k; ++f) {
+            sU[u[t] * k + f] += dU[f]; sV[i[t] * k + f] += dI[f]; sV[j[t] * k + f] += dJ[f];
+            nu2 += dU[f] * dU[f]; ni2 += dI[f] * dI[f]; nj2 += dJ[f] * dJ[f];
+            if (has_v) { sV[v[t] * k + f] += dV[f]; nv2 += dV[f] * dV[f]; }
+        }
+        pU[u[t]] += sqrt(nu2); pV[i[t]] += sqrt(ni2); pV[j[t]] += sqrt(nj2);
+        ++tU[u[t]]; ++tV[i[t]]; ++tV[j[t]];
+        if (has_v) { pV[v[t]] += sqrt(nv2); ++tV[v[t]]; }
+    }
+    free(buf);
+}
+
 int oracle_num_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

@@ -133,6 +133,18 @@ def _bind(L):
         L.oracle_mf_jacobi_f64.argtypes = [i64p, i64p, f32p, C.c_int64, f32p, f32p, f32p, f32p, C.c_int, C.c_double, C.c_double,
                                            C.c_double, C.c_int, C.c_double] + [f64p_] * 8 + [i64p] * 4 + [f64p_]
         L.oracle_mf_jacobi_f64.restype = None
+        L.oracle_vebpr_hogwild_sample.argtypes = [C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32,
+                                                  i64p, u32p, i64p]
+        L.oracle_vebpr_hogwild_sample.restype = None
+        L.oracle_vebpr_hogwild_sample_owned.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                        C.c_int64, C.c_int64, i64p, u32p, i64p]
+        L.oracle_vebpr_hogwild_sample_owned.restype = None
+        L.oracle_vebpr_apply_seq_f64.argtypes = [i64p] * 5 + [C.c_int64, f64p_, f64p_, C.c_int, C.c_double, C.c_double,
+                                                              C.c_double, C.c_int, C.c_int, C.c_int64, C.c_double]
+        L.oracle_vebpr_apply_seq_f64.restype = None
+        L.oracle_vebpr_jacobi_f64.argtypes = [i64p] * 4 + [C.c_int64, f32p, f32p, C.c_int, C.c_double, C.c_double,
+                                                           C.c_double] + [f64p_] * 4 + [i64p] * 2 + [f64p_]
+        L.oracle_vebpr_jacobi_f64.restype = None
         L.oracle_num_threads.restype = C.c_int
         L.oracle_sizeof_mt.restype = C.c_int
     return L
@@ -743,4 +755,100 @@ def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, ne
     out = dict(u=u[keep], i=i[keep], j=j[keep], skipped=int((~keep).sum()))
     if shared is not None:
         out["shared"] = shared[keep]
+    return out
+
+
+def vebpr_hogwild_sample(seed, epoch, s0, n, n_pos, n_items):
+    """unowned hogwild VEBPR sampler (csrc/vebpr.inc): (interaction index, view word, negative item) of samples [s0, s0 + n)"""
+    ii, w2, jj = np.empty(n, np.int64), np.empty(n, np.uint32), np.empty(n, np.int64)
+    lib().oracle_vebpr_hogwild_sample(int(seed), int(epoch), int(s0), int(n), int(n_pos), int(n_items), ii, w2, jj)
+    return ii, w2, jj
+
+
+def vebpr_hogwild_sample_owned(seed, epoch, wave_id, length, n_items, lo, hi):
+    """owned form: (index into the wave's slice, view word, negative item) of the wave's local samples [lo, hi)"""
+    r, w2, jj = np.empty(hi - lo, np.int64), np.empty(hi - lo, np.uint32), np.empty(hi - lo, np.int64)
+    lib().oracle_vebpr_hogwild_sample_owned(int(seed), int(epoch), int(wave_id), int(length), int(n_items), int(lo), int(hi),
+                                            r, w2, jj)
+    return r, w2, jj
+
+
+def hogwild_quadruples(form, seed, epoch, indptr, indices, v_indptr, v_indices, n_items, ownership=None):
+    """The non-skipped (u, i, v, j) that ONE hogwild VEBPR epoch applies — cornac_hip_vebpr_fit_epochs(1, ...) is always a
+    whole epoch — from the restatements of the device sampler above; integer work, exact.
+
+      form "unowned"  samples [0, nnz) in sample order
+      form "owned"    every wave's whole slice, wave by wave; ownership = (wave_ptr, own_u, own_i) as hogwild_ownership
+                      restates them for the launch's wave count
+
+    v = -1 for users without views, else v_indices[v_indptr[u] + ((w2 * nv) >> 32)].  A sample is skipped when its
+    negative is in the user's purchase row or, for users with views, in the view row.  Returns a dict: u, i, v, j (int64, the
+    restatement's order), draws (samples drawn), skipped (the epoch's skip count) = skipped_purchase (negative in the
+    purchase row) + skipped_view_only (in the view row alone); "owned" adds shared (the user is split over the waves:
+    atomics on its row)."""
+    indptr = np.ascontiguousarray(indptr, np.int32)
+    indices = np.ascontiguousarray(indices, np.int32)
+    v_indptr = np.ascontiguousarray(v_indptr, np.int64)
+    v_indices = np.ascontiguousarray(v_indices, np.int32)
+    nnz = len(indices)
+    shared = None
+    if form == "unowned":
+        user_ids = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+        ii, w2, j = vebpr_hogwild_sample(seed, epoch, 0, nnz, nnz, n_items)
+        u, i = user_ids[ii], indices[ii].astype(np.int64)
+    elif form == "owned":
+        wave_ptr, own_u, own_i = ownership
+        lens = np.diff(wave_ptr)
+        us, is_, ws, js = [], [], [], []
+        for w in np.flatnonzero(lens > 0):
+            r, w2w, jw = vebpr_hogwild_sample_owned(seed, epoch, int(w), int(lens[w]), n_items, 0, int(lens[w]))
+            us.append(own_u[wave_ptr[w] + r])
+            is_.append(own_i[wave_ptr[w] + r])
+            ws.append(w2w)
+            js.append(jw)
+        u, i, j = (np.concatenate(p).astype(np.int64) for p in (us, is_, js))
+        w2 = np.concatenate(ws)
+        shared = u < 0
+        u = np.where(shared, ~u, u)
+    else:
+        raise ValueError("form is 'unowned' or 'owned': %r" % (form,))
+    v0 = v_indptr[u]
+    nv = v_indptr[u + 1] - v0
+    has_v = nv > 0
+    v = np.full(len(u), -1, np.int64)
+    pos = v0[has_v] + ((w2[has_v].astype(np.uint64) * nv[has_v].astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+    v[has_v] = v_indices[pos]
+    in_purchase = _csr_has(indptr, indices, n_items, u, j)
+    in_view = _csr_has(v_indptr, v_indices, n_items, u, j) if v_indptr[-1] > 0 else np.zeros(len(u), bool)
+    keep = ~(in_purchase | in_view)
+    out = dict(u=u[keep], i=i[keep], v=v[keep], j=j[keep], draws=len(u), skipped=int((~keep).sum()),
+               skipped_purchase=int(in_purchase.sum()), skipped_view_only=int((in_view & ~in_purchase).sum()))
+    if shared is not None:
+        out["shared"] = shared[keep]
+    return out
+
+
+def vebpr_apply_seq_f64(quad, order, U, V, lr, reg, alpha, fault=0, mark=None):
+    """float64 tables (modified in place) after the quadruples' hogwild VEBPR updates, one after another in `order`;
+    fault = 1 + its index in vebpr_step_oracle.FAULTS; mark = (table "U" | "V", row, sign): that row's last update is
+    applied once more with that factor"""
+    u, i, v, j = (np.ascontiguousarray(a, np.int64) for a in quad)
+    order = np.ascontiguousarray(order, np.int64)
+    assert U.dtype == V.dtype == np.float64 and U.flags.c_contiguous and V.flags.c_contiguous and len(order) <= len(u)
+    tab, row, sign = (0, 0, 0.0) if mark is None else ({"U": 1, "V": 2}[mark[0]], int(mark[1]), float(mark[2]))
+    lib().oracle_vebpr_apply_seq_f64(u, i, v, j, order, len(order), U, V, U.shape[1], float(lr), float(reg), float(alpha),
+                                     int(fault), tab, row, sign)
+
+
+def vebpr_jacobi_f64(quad, tables, lr, reg, alpha):
+    """every quadruple's deltas from the float32 start tables, summed per row in float64: {"U" | "V": dict(sum, touches,
+    path), "x": [n, 3] clamped scores x_ij, x_iv, x_vj} (oracle/vebpr_step_oracle.py `jacobi`)"""
+    u, i, v, j = (np.ascontiguousarray(a, np.int64) for a in quad)
+    U, V = (np.ascontiguousarray(t, np.float32) for t in tables[:2])
+    out = {tab: dict(sum=np.zeros(t.shape), touches=np.zeros(len(t), np.int64), path=np.zeros(len(t)))
+           for tab, t in (("U", U), ("V", V))}
+    out["x"] = np.zeros((len(u), 3))
+    lib().oracle_vebpr_jacobi_f64(u, i, v, j, len(u), U, V, U.shape[1], float(lr), float(reg), float(alpha),
+                                  *[out[tab]["sum"] for tab in "UV"], *[out[tab]["path"] for tab in "UV"],
+                                  *[out[tab]["touches"] for tab in "UV"], out["x"])
     return out
