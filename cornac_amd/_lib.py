@@ -71,6 +71,10 @@ SYMBOLS = [
     "cornac_hip_score_block", "cornac_hip_rank_topk", "cornac_hip_rank_topk_device", "cornac_hip_score_pairs",
     "cornac_hip_scorer_set_exclusions", "cornac_hip_rank_topk_resident", "cornac_hip_scorer_host_buffer",
     "cornac_hip_rank_positions",
+    "cornac_hip_knn_sim_create", "cornac_hip_knn_sim_destroy", "cornac_hip_knn_sim_run", "cornac_hip_knn_sim_nnz",
+    "cornac_hip_knn_sim_get",
+    "cornac_hip_knn_scorer_create", "cornac_hip_knn_scorer_destroy", "cornac_hip_knn_scorer_score_users",
+    "cornac_hip_knn_scorer_score_pairs",
 ]
 
 
@@ -288,6 +292,15 @@ def lib():
         L.cornac_hip_scorer_set_exclusions.argtypes = [_vp, _vp, _vp]
         L.cornac_hip_scorer_host_buffer.argtypes = [_vp, C.c_size_t, C.POINTER(_vp)]
         L.cornac_hip_rank_topk_resident.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, _vp]
+        L.cornac_hip_knn_sim_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, _vp]
+        L.cornac_hip_knn_sim_destroy.argtypes = [_vp]
+        L.cornac_hip_knn_sim_run.argtypes = [_vp, C.c_int64]
+        L.cornac_hip_knn_sim_nnz.argtypes = [_vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_knn_sim_get.argtypes = [_vp, _vp, _vp, _vp]
+        L.cornac_hip_knn_scorer_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, C.c_int64] + [_vp] * 6 + [C.c_int]
+        L.cornac_hip_knn_scorer_destroy.argtypes = [_vp]
+        L.cornac_hip_knn_scorer_score_users.argtypes = [_vp, _vp, C.c_int64, C.c_int, _vp]
+        L.cornac_hip_knn_scorer_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int, _vp]
         _lib = L
     return _lib
 
@@ -1174,3 +1187,85 @@ class WmfTrainer:
         ms = C.c_double()
         check(lib().cornac_hip_wmf_last_timing(self.h, C.byref(ms)))
         return ms.value
+
+
+KNN_MAX_K = 64   # CORNAC_HIP_KNN_MAX_K
+
+
+def _csr_arrays(mat):
+    """(indptr int64, indices int32, data float64) of a scipy CSR with sorted indices; the arrays are kept alive by the
+    caller for the length of the call"""
+    mat = mat.tocsr()
+    if not mat.has_sorted_indices:
+        mat = mat.sorted_indices()
+    return (np.ascontiguousarray(mat.indptr, np.int64), np.ascontiguousarray(mat.indices, np.int32),
+            np.ascontiguousarray(mat.data, np.float64))
+
+
+class KnnSimilarity:
+    """Owner of a cornac_hip_knn_sim_t handle: `compute_similarity` of cornac/models/knn/similarity.pyx:51-105 over the rows
+    of a scipy CSR, as a scipy CSR of float64."""
+
+    def __init__(self, W, device=0):
+        self.shape = tuple(int(x) for x in W.shape)
+        self._csr = _csr_arrays(W)
+        self.h = _vp()
+        check(lib().cornac_hip_knn_sim_create(C.byref(self.h), device, self.shape[0], self.shape[1],
+                                              *[_ptr(a) for a in self._csr]))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h and lib is not None:
+            lib().cornac_hip_knn_sim_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def run(self, rows_per_pass=0):
+        """rows_per_pass: rows whose accumulators are held at once (0: chosen from the free device memory)"""
+        import scipy.sparse as sp
+
+        check(lib().cornac_hip_knn_sim_run(self.h, int(rows_per_pass)))
+        nnz = C.c_int64()
+        check(lib().cornac_hip_knn_sim_nnz(self.h, C.byref(nnz)))
+        n = self.shape[0]
+        indptr, indices, data = np.empty(n + 1, np.int64), np.empty(nnz.value, np.int32), np.empty(nnz.value, np.float64)
+        check(lib().cornac_hip_knn_sim_get(self.h, _ptr(indptr), _ptr(indices), _ptr(data)))
+        return sp.csr_matrix((data, indices, indptr.astype(np.int32) if nnz.value < 2 ** 31 else indptr), shape=(n, n))
+
+
+class KnnScorer:
+    """Owner of a cornac_hip_knn_scorer_t handle: `compute_score` / `compute_score_single` (similarity.pyx:108-201) for the
+    neighbour table N [n_items x n_neighbours] and the query table Q [n_users x n_neighbours], both scipy CSR."""
+
+    MAX_K = KNN_MAX_K
+
+    def __init__(self, N, Q, user_mode, device=0):
+        self.n_items, self.n_neighbours = (int(x) for x in N.shape)
+        self.n_users = int(Q.shape[0])
+        assert int(Q.shape[1]) == self.n_neighbours, "N and Q must have the same number of columns"
+        n, q = _csr_arrays(N), _csr_arrays(Q)
+        self.h = _vp()
+        check(lib().cornac_hip_knn_scorer_create(C.byref(self.h), device, self.n_items, self.n_neighbours, self.n_users,
+                                                 *[_ptr(a) for a in n + q], int(bool(user_mode))))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h and lib is not None:
+            lib().cornac_hip_knn_scorer_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def score_users(self, users, k):
+        """weighted averages [n, n_items] float64"""
+        users = np.ascontiguousarray(users, np.int32)
+        out = np.empty((len(users), self.n_items), np.float64)
+        check(lib().cornac_hip_knn_scorer_score_users(self.h, _ptr(users), len(users), int(k), _ptr(out)))
+        return out
+
+    def score_pairs(self, users, items, k):
+        """weighted averages [n] float64 for the pairs (users[p], items[p])"""
+        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
+        assert len(users) == len(items)
+        out = np.empty(len(users), np.float64)
+        check(lib().cornac_hip_knn_scorer_score_pairs(self.h, _ptr(users), _ptr(items), len(users), int(k), _ptr(out)))
+        return out

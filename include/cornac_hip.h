@@ -719,6 +719,56 @@ int cornac_hip_rank_positions(cornac_hip_scorer_t h, const int32_t *users, int64
  * the kernels (hipEvent) in *ms. */
 int cornac_hip_rank_topk_device(cornac_hip_scorer_t h, int64_t u0, int64_t n, int topk, int repeats, double *ms);
 
+/* ------------------------------------------------------------------------- *
+ * Neighbourhood models (UserKNN / ItemKNN), float64 throughout.
+ * Replaces: compute_similarity, compute_score and compute_score_single of
+ *           cornac/models/knn/similarity.pyx:51-201 with the TopK / SparseNeighbors
+ *           helpers of cornac/models/knn/similarity.h, as called by
+ *           cornac/models/knn/recom_knn.py:205, :240-261, :382, :413-434.
+ * Every CSR here has sorted column indices without repeats (checked).
+ * ------------------------------------------------------------------------- */
+typedef struct cornac_hip_knn_sim *cornac_hip_knn_sim_t;
+typedef struct cornac_hip_knn_scorer *cornac_hip_knn_scorer_t;
+/* largest neighbourhood size k of the scoring calls */
+#define CORNAC_HIP_KNN_MAX_K 64
+
+/* compute_similarity(data_mat) (similarity.pyx:51-105; its k argument is unused there): W is the CSR
+ * [n_rows x n_cols] of data_mat.  For every row r and every row i sharing a column with it,
+ * S[r,i] = sum x*w over the shared columns in r's stored order, divided (where it is != 0) by sqrt(d1 * d2) with d1 / d2
+ * the sums of w*w / x*x over the shared columns whose two values are both != 0 -- the quotient of the extension as the
+ * reference compiles it (-ffast-math, setup.py:128-138).  The result holds exactly the entries that are != 0, ascending
+ * column indices, the diagonal included. */
+int cornac_hip_knn_sim_create(cornac_hip_knn_sim_t *out, int device, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
+                              const int32_t *indices, const double *data);
+int cornac_hip_knn_sim_destroy(cornac_hip_knn_sim_t h);
+/* rows_per_pass rows at a time, each with three accumulators of n_rows doubles in device scratch (the reference's
+ * per-thread denom1 / denom2 and its dense sim_mat row, similarity.pyx:66-74); 0 = as many as half of the free device
+ * memory holds.  The result does not depend on it, and a repeated run gives the same bits.  Fails with
+ * CORNAC_HIP_ERR_HIP and a message naming the buffer when the scratch or the result cannot be allocated. */
+int cornac_hip_knn_sim_run(cornac_hip_knn_sim_t h, int64_t rows_per_pass);
+/* entries of the result of the last run, then the result itself: indptr[n_rows + 1], indices[nnz], data[nnz]
+ * (csr_matrix(sim_mat), similarity.pyx:102) */
+int cornac_hip_knn_sim_nnz(cornac_hip_knn_sim_t h, int64_t *nnz);
+int cornac_hip_knn_sim_get(cornac_hip_knn_sim_t h, int64_t *indptr, int32_t *indices, double *data);
+
+/* compute_score / compute_score_single (similarity.pyx:108-201).  N: the neighbour table, CSR [n_items x n_neighbours]
+ * (UserKNN: iu_mat; ItemKNN: sim_mat); Q: CSR [n_users x n_neighbours] whose row u, made dense, is the call's sim_arr
+ * (UserKNN: sim_mat; ItemKNN: ui_mat).  The candidates of item i are the entries (nn, s) of N's row i with
+ * Q[u, nn] != 0 (a stored zero is no candidate); (weight, rating) = (Q[u,nn], s) if user_mode, else (s, Q[u,nn]).  The
+ * survivors are those of the reference's heap of k pairs fed in reverse stored order (similarity.h:15-38, :62-79), ties
+ * at the k-th weight included; out = sum w*s / (sum |w| + 1e-8) over them, 0 without candidates.  1 <= k <=
+ * CORNAC_HIP_KNN_MAX_K.  Weights must not be NaN. */
+int cornac_hip_knn_scorer_create(cornac_hip_knn_scorer_t *out, int device, int64_t n_items, int64_t n_neighbours,
+                                 int64_t n_users, const int64_t *n_indptr, const int32_t *n_indices, const double *n_data,
+                                 const int64_t *q_indptr, const int32_t *q_indices, const double *q_data, int user_mode);
+int cornac_hip_knn_scorer_destroy(cornac_hip_knn_scorer_t h);
+/* out[n x n_items]: compute_score for each listed user (similarity.pyx:154-201) */
+int cornac_hip_knn_scorer_score_users(cornac_hip_knn_scorer_t h, const int32_t *users, int64_t n, int k, double *out);
+/* out[n]: compute_score_single for each (users[p], items[p]) (similarity.pyx:109-150); the bits of the matching
+ * score_users entry */
+int cornac_hip_knn_scorer_score_pairs(cornac_hip_knn_scorer_t h, const int32_t *users, const int32_t *items, int64_t n, int k,
+                                      double *out);
+
 #ifdef __cplusplus
 }
 #endif
