@@ -689,7 +689,8 @@ def _csr_has(indptr, indices, n_items, u, j):
 
 
 def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, neg_pop=False, ownership=None, n_bins=None,
-                     hot_x1000=75, share=None, strata_groups=16, hot_cost_x16=32, tables=None):
+                     hot_x1000=75, share=None, strata_groups=16, hot_cost_x16=32, tables=None, deal=None, bins=None,
+                     rank_item=None):
     """The non-skipped (u, i, j) that ONE hogwild launch applies — cornac_hip_bpr_hogwild_enqueue(n) at sample offset
     s_begin of `epoch`, s_begin + n <= nnz — from the restatements of the device samplers above; integer work, exact.
 
@@ -698,6 +699,11 @@ def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, ne
                      (hogwild_sample_owned), wave by wave; ownership = BprTrainer.debug_ownership()
       form "ldsbin"  the draws [n_b s_begin / nnz, n_b (s_begin + n) / nnz) of every bin b (resident and passing bins:
                      the caller names n_bins and, for passing bins, share), bin by bin
+      form "ldsbin", deal = (deal_seed, layout_epoch), bins = [(lo, hi), ...]: ONE conveyor launch —
+                     cornac_hip_bpr_conveyor_enqueue(epoch, layout_epoch, blocks) — whose ranges are the bins [lo, hi) in
+                     launch order (block B of bins_per_block bins: (B bpb, (B + 1) bpb)).  The deal's key comes from `deal`,
+                     the draws' from (seed, epoch); no item is hot; a launch is the whole epoch of its bins (s_begin = 0,
+                     n = nnz); rank_item replaces the tables' popularity order (conveyor_setup's explicit order).
 
     Returns a dict: u, i, j (int64 arrays, the restatement's order), skipped (the launch's skip count); "ldsbin" adds bin
     (the bin that drew each triplet) and hot (its positive came from the hot list); "owned" adds shared (its user is
@@ -707,22 +713,39 @@ def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, ne
     nnz, s_begin, n = len(indices), int(s_begin), int(n)
     assert 0 <= s_begin and n >= 0 and s_begin + n <= nnz
     if form == "ldsbin":
+        conveyor = deal is not None
+        if conveyor:
+            assert bins and s_begin == 0 and n == nnz, "a conveyor launch is the whole epoch of its ranges' bins"
+            hot_x1000 = 10 ** 9
         t = tables if tables is not None else ldsbin_tables(indptr, indices, n_items, n_bins, hot_x1000, share)
-        key = int(lib().oracle_ldsbin_key(int(seed), int(epoch)))
-        cap = n + 2 * int(n_bins) + 8
-        u, i, j, b = (np.empty(cap, np.int32) for _ in range(4))
-        hot = np.empty(cap, np.uint8)
-        draws, kept = C.c_int64(), C.c_int64()
-        skipped = lib().oracle_ldsbin_draws(int(seed), int(epoch), key, int(n_bins), int(n_items), int(t["n_hot"]),
-                                            int(ldsbin_n_strata(n_items, n_bins, strata_groups)), int(hot_cost_x16),
-                                            t["rank_item"], t["cptr"], t["cusers"], t["hot_u"], t["hot_i"],
-                                            int(t["n_hot_inter"]), t["indptr"], t["indices"], C.byref(draws), None, None,
-                                            int(bool(neg_pop)), 0, int(n_bins), s_begin, n, nnz, u.ctypes.data, i.ctypes.data,
-                                            j.ctypes.data, b.ctypes.data, hot.ctypes.data, cap, C.byref(kept))
-        m = int(kept.value)
-        assert m <= cap and draws.value == nnz
-        return dict(u=u[:m].astype(np.int64), i=i[:m].astype(np.int64), j=j[:m].astype(np.int64), skipped=int(skipped),
-                    bin=b[:m].astype(np.int64), hot=hot[:m].astype(bool))
+        order = t["rank_item"] if rank_item is None else np.ascontiguousarray(rank_item, np.int32)
+        assert not conveyor or t["n_hot"] == 0
+        assert len(order) == n_items
+        key = int(lib().oracle_ldsbin_key(*((int(seed), int(epoch)) if not conveyor else (int(deal[0]), int(deal[1])))))
+        parts, skipped, drawn = [], 0, 0
+        for lo, hi in (bins if conveyor else [(0, int(n_bins))]):
+            assert 0 <= lo < hi <= n_bins
+            cap = n + 2 * int(n_bins) + 8
+            u, i, j, b = (np.empty(cap, np.int32) for _ in range(4))
+            hot = np.empty(cap, np.uint8)
+            draws, kept = C.c_int64(), C.c_int64()
+            skipped += int(lib().oracle_ldsbin_draws(
+                int(seed), int(epoch), key, int(n_bins), int(n_items), int(t["n_hot"]),
+                int(ldsbin_n_strata(n_items, n_bins, strata_groups)), int(hot_cost_x16), order, t["cptr"], t["cusers"],
+                t["hot_u"], t["hot_i"], int(t["n_hot_inter"]), t["indptr"], t["indices"], C.byref(draws), None, None,
+                int(bool(neg_pop)), int(lo), int(hi), s_begin, n, nnz, u.ctypes.data, i.ctypes.data, j.ctypes.data,
+                b.ctypes.data, hot.ctypes.data, cap, C.byref(kept)))
+            m = int(kept.value)
+            assert m <= cap
+            drawn += int(draws.value)
+            parts.append([a[:m] for a in (u, i, j, b, hot)])
+        assert conveyor or drawn == nnz
+        u, i, j, b, hot = (np.concatenate([p[q] for p in parts]) for q in range(5))
+        out = dict(u=u.astype(np.int64), i=i.astype(np.int64), j=j.astype(np.int64), skipped=skipped, bin=b.astype(np.int64),
+                   hot=hot.astype(bool))
+        if conveyor:
+            out["draws"] = drawn  # the ranges' interactions: every one is drawn (or skipped) once per epoch
+        return out
     n_neg = nnz if neg_pop else int(n_items)
     if form == "fused":
         user_ids = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))

@@ -1,10 +1,12 @@
 """Inputs, references and checks of the hogwild BPR step tests, in ONE place: tests/test_bpr_step_gpu.py runs the cases on
 the device, tests/test_bpr_step_cpu.py proves — from the restatements and the float64 step alone — that every case is a
-fair test, that the tolerances below follow their rules, and that the checks reject nine deliberately wrong updates.
+fair test, that the tolerances below follow their rules, and that the checks reject nine deliberately wrong updates (and,
+for the conveyor's block buffers, four wrong uses of them).
 
 A case = Zipf interactions + normal tables with real scores (z well away from 0.5) + ONE launch of `n` samples at sample
-offset `s_begin` of epoch 0, whose non-skipped triplets oracle.hogwild_triplets names before anything runs.  The launch is
-made three times from the same start tables:
+offset `s_begin` of epoch 0 (conveyor cases: ONE conveyor_enqueue over 1 to 8 blocks, whose item rows live in block
+buffers: `pack` / `unpack` / `conveyor_tables`), whose non-skipped triplets oracle.hogwild_triplets names before anything
+runs.  The launch is made three times from the same start tables:
 
   Z  lr = 0             tables bit-identical; skip counter == the restatement's; `correct` == #(x > 0) in float64, give or
                         take the triplets whose |x| is below the float32 score's a-priori error bound
@@ -48,6 +50,13 @@ LR_A, LR_B, REG = 0.05, 2.0 ** -12, 0.01
 #   delta lr (z - reg b) is small (z = 0.01: path 1e-6) beside the rounding of its one float32 add onto |b| = 1.4 (3.4e-8,
 #   under ulp / 2 = 6e-8): that is the floor term of the tolerance; net of it the bias rows lie within 0.0041 / 0.0049 of
 #   their path, like U, V and the float64 orders.
+# Conveyor (cornac_hip_bpr_conveyor_enqueue; a launch = the whole epoch of its blocks' bins, 1 527 .. 3 234 triplets):
+#   float32 step vs float64 step over the clean rows 2.9e-8 .. 6.1e-8; |sequential - jacobi| / path, three orders: 0.0023
+#   (k = 40) .. 0.0056 (k = 256, popularity), 0.0065 heavy  ->  C = 0.01 .. 0.03 below.  33 .. 37 % of the triplets clean (a
+#   bin draws its positives with replacement: at most 1 / e can be), 1 % with popularity negatives, 12 % heavy.
+# MI355X, conveyor: `correct` inside the float64 interval in all 15 cases (one number in 13); launch A, clean rows: U 5.9e-8,
+#   V 5.9e-8, B 6.1e-8; launch B, error / tolerance: U 0.14, V 0.22 (conv_k40), B 0.59 (conv_k192; 0.43 conv_k40, 0.40
+#   conv_ranges8_k64: rows touched once, the floor term as above); layouts equal to the oracle's, no lock time-outs.
 T_CLEAN = 5e-7
 C = {
     "fused_k3": 0.03, "fused_k7": 0.02, "fused_k16": 0.02, "fused_k20": 0.02,
@@ -57,6 +66,9 @@ C = {
     "lds_k100": 0.02, "lds_k192": 0.02, "lds_k200": 0.02, "lds_nobias_k64": 0.005,
     "lds_pop_k100": 0.007, "lds_partial_k64": 0.02, "lds_wide_k64": 0.2, "pass_k128": 0.2, "pass_k64": 0.2,
     "owned_k64": 0.03, "owned_k100": 0.03,
+    "conv_k40": 0.01, "conv_k64": 0.02, "conv_k100": 0.02, "conv_k192": 0.03, "conv_k256": 0.02,
+    "conv_pop_k64": 0.02, "conv_pop_k100": 0.02, "conv_pop_k192": 0.02, "conv_pop_k256": 0.03, "conv_nobias_k192": 0.02,
+    "conv_ranges3_k100": 0.02, "conv_ranges8_k64": 0.02, "conv_pad_k64": 0.02, "conv_order_k64": 0.02, "conv_heavy_k64": 0.03,
 }
 
 
@@ -72,6 +84,22 @@ def _owned(k, **kw):
 
 def _lds(k, **kw):
     return dict(dict(form="ldsbin", k=k, nu=20_000, ni=30_720, nnz=300_000, zipf=0.8, n=2048, flags=_lib.FORM_LDSBIN), **kw)
+
+
+def _conv(k, **kw):
+    """ONE conveyor launch (cornac_hip_bpr_conveyor_enqueue) over `blocks` of `n_blocks`: the whole epoch of those blocks'
+    bins, so the data are sparse (8 192 interactions over 131 072 items) to keep the launch at some 2 000 triplets.  The
+    draws are keyed by (seed, epoch), the deal by (deal_seed, layout_epoch): all four differ in every case."""
+    return dict(dict(form="conveyor", kind="sparse", k=k, nu=100_000, ni=131_072, nnz=8_192, zipf=0.1, user_sigma=0.5, n=None,
+                     s_begin=0, flags=0, n_blocks=4, blocks=(2,), epoch=5, layout_epoch=3, deal_seed=0xDEA10000 + k,
+                     order_seed=None, heavy=None), **kw)
+
+
+def _conv_pop(k, **kw):
+    # the negative of a popularity draw is the item of another interaction of the bin, and every such item is a positive
+    # of the same launch too: next to no triplet is clean, so launch B carries these cases (clean_share=False: the clean
+    # triplets that exist are checked all the same)
+    return _conv(k, kind="pop", neg_pop=True, clean_share=False, **kw)
 
 
 # One case per kernel instantiation the dispatchers return (csrc/bpr.hip pick_hogwild_kernel, pick_ldsbin_kernel).
@@ -112,8 +140,23 @@ SPECS = {
     # x 4 waves at k = 64 (R = 1) and x 6 x 4 at k = 100 (R = 2), the occupancy of the two instantiations; the device test
     # takes the count from debug_ownership() and rebuilds the case if the device runs another grid.
     "owned_k64": _owned(64, waves=4096), "owned_k100": _owned(100, waves=6144),
+    # the conveyor (csrc/bpr.hip pick_ldsbin_kernel(conv = true)): R = 1..4 with uniform and with popularity negatives, and
+    # the address arithmetic of the block buffers
+    "conv_k40": _conv(40), "conv_k64": _conv(64), "conv_k100": _conv(100), "conv_k192": _conv(192),
+    "conv_k256": _conv(256),  # (2 344 bins of 56 rows: the LDS decides the plan, not the candidates)
+    "conv_pop_k64": _conv_pop(64), "conv_pop_k100": _conv_pop(100), "conv_pop_k192": _conv_pop(192),
+    "conv_pop_k256": _conv_pop(256),
+    "conv_nobias_k192": _conv(192, use_bias=False),
+    "conv_ranges3_k100": _conv(100, n_blocks=16, blocks=(11, 2, 7)),  # three ranges, not in ascending order
+    "conv_ranges8_k64": _conv(64, n_blocks=32, blocks=(30, 1, 17, 8, 0, 31, 12, 5)),  # kLbMaxRanges
+    "conv_pad_k64": _conv(64, ni=130_072),  # 2 032 bins of 65 slots: the last group has 24 items, so most bins end in a pad slot
+    "conv_order_k64": _conv(64, order_seed=77),  # conveyor_setup's explicit item order: a seeded permutation
+    # skipped draws and hot user rows: 8 users of 600 interactions each on top (denser data would leave nothing clean)
+    "conv_heavy_k64": _conv(64, kind="heavy", ni=65_536, heavy=(8, 600), clean_share=False),
 }
 NAMES = list(SPECS)
+CONVEYOR_NAMES = [name for name in NAMES if SPECS[name]["form"] == "conveyor"]
+PAD = -7.75  # what the pad slots of the block buffers hold (finite: a pad slot read as a row shows in the checks, not as a NaN)
 
 
 def ldsbin_plan(ni, nnz, k, cus=MI355X_CUS, min_candidates=48, max_rounds=4, pass_min_draws_x100=200):
@@ -143,9 +186,68 @@ def ldsbin_plan(ni, nnz, k, cus=MI355X_CUS, min_candidates=48, max_rounds=4, pas
     return dict(bins=bins, cap=cap, passing=True)
 
 
+def conveyor_plan(ni, k, n_blocks, cus=MI355X_CUS, min_candidates=48, pass_waves=8, pass_kb=64):
+    """the conveyor branch of csrc/bpr.hip ldsbin_plan restated (defaults of the pass config): dict(bins, bpb, cap) or None.
+    tests/test_bpr_step_gpu.py holds it against what conveyor_setup returns before it launches.  The cases' shapes keep
+    n_items / 64 <= 2 x CUs x n_blocks, so their plans do not depend on the device's CU count."""
+    if k > 256:
+        return None
+    kp = (k + 63) // 64 * 64
+    fixed = 4 + pass_waves * 3 * 64 * 4
+    if pass_kb * 1024 <= fixed:
+        return None
+    cap_lds = (pass_kb * 1024 - fixed) // ((kp + 5) * 4)
+    cap_min = max(min_candidates, 16)
+    if cap_lds < cap_min:
+        return None
+    bins = max(-(-ni // cap_lds), min(ni // (cap_min + cap_min // 3), 2 * cus * n_blocks))
+    bins = max(1, -(-bins // n_blocks)) * n_blocks
+    cap = -(-ni // bins)
+    if cap > cap_lds or bins > 1 << 22 or bins * cap >= 1 << 31:
+        return None
+    return dict(bins=bins, bpb=bins // n_blocks, cap=cap)
+
+
+def pack(V, B, slot_item, blocks, bpb, cap, into=None, bias_at=None):
+    """the block buffers of `blocks` (csrc/bpr_ldsbin.inc LdsBinArgs::conv_rows): per block bpb x cap x k row floats in (bin,
+    slot) order, then bpb x cap biases; slot s of the deal holds item slot_item[s], pad slots (-1) hold PAD.  into = existing
+    buffers, one per block of `blocks`: only the slots that hold an item are written.  bias_at: where the bias area begins (a
+    deliberately wrong kernel's; default bpb x cap x k).  Returns a list of float32 arrays."""
+    k, w = V.shape[1], bpb * cap
+    bias_at = w * k if bias_at is None else bias_at
+    out = []
+    for n, blk in enumerate(blocks):
+        items = slot_item[blk * w:(blk + 1) * w]
+        ok = np.flatnonzero(items >= 0)
+        buf = np.full(w * k + w, PAD, np.float32) if into is None else into[n]
+        buf[:w * k].reshape(w, k)[ok] = V[items[ok]]
+        buf[bias_at + ok] = B[items[ok]]
+        out.append(buf)
+    return out
+
+
+def unpack(bufs, V, B, slot_item, blocks, bpb, cap, bias_at=None):
+    """copies of (V, B) with the rows and biases of the items of `blocks` taken from their buffers"""
+    k, w = V.shape[1], bpb * cap
+    bias_at = w * k if bias_at is None else bias_at
+    V, B = np.array(V, np.float32), np.array(B, np.float32)
+    for buf, blk in zip(bufs, blocks):
+        items = slot_item[blk * w:(blk + 1) * w]
+        ok = np.flatnonzero(items >= 0)
+        V[items[ok]] = buf[:w * k].reshape(w, k)[ok]
+        B[items[ok]] = buf[bias_at + ok]
+    return V, B
+
+
 @functools.lru_cache(maxsize=4)
-def _data(nu, ni, nnz, zipf, user_sigma=1.0):
+def _data(nu, ni, nnz, zipf, user_sigma=1.0, heavy=None):
     users, items = synth.zipf_interactions(nu, ni, nnz, zipf, 11, user_sigma)
+    if heavy is not None:  # (count, degree): that many users get `degree` further items each
+        rs = np.random.RandomState(13)
+        hu = rs.choice(nu, heavy[0], replace=False)
+        keys = np.concatenate([users * ni + items] + [int(u) * ni + rs.choice(ni, heavy[1], replace=False) for u in hu])
+        keys = np.unique(keys)
+        users, items = keys // ni, keys % ni
     return synth.csr_from_sorted(users, items, nu)
 
 
@@ -163,12 +265,13 @@ class Case:
 
     def __init__(self, name, cus=MI355X_CUS, waves=None):
         sp = dict(dict(use_bias=True, neg_pop=False, s_begin=12_345, seed=0x5EED0000 + len(name), max_rounds=4,
-                       min_candidates=48, clean_share=True, only_b=False, user_sigma=1.0), **SPECS[name])
+                       min_candidates=48, clean_share=True, only_b=False, user_sigma=1.0, heavy=None, kind=None), **SPECS[name])
         self.name, self.spec = name, sp
         for key, v in sp.items():
             setattr(self, key, v)
         self.total_items = self.ni + 37  # item rows beyond the trained range: no launch may touch them
-        self.indptr, self.indices = _data(self.nu, self.ni, self.nnz, self.zipf, self.user_sigma)
+        self.indptr, self.indices = _data(self.nu, self.ni, self.nnz, self.zipf, self.user_sigma, self.heavy)
+        self.nnz = len(self.indices)
         self.tables = _tables(name, self.nu, self.total_items, self.k)
         self.neg_population = _lib.NEG_POPULARITY if self.neg_pop else _lib.NEG_UNIFORM
         kw = {}
@@ -185,8 +288,29 @@ class Case:
             self.n = -(-self.nnz // tmax) - self.s_begin
             assert tmax * self.s_begin // self.nnz == 0 and (tmax == 1 or tmax * (self.s_begin + self.n) // self.nnz == 1)
             kw = dict(ownership=self.ownership)
-        t = orc.hogwild_triplets(self.form, self.seed, 0, self.s_begin, self.n, self.indptr, self.indices, self.ni,
+        form, epoch = self.form, 0
+        if self.form == "conveyor":
+            self.plan = conveyor_plan(self.ni, self.k, self.n_blocks, cus, self.min_candidates)
+            assert self.plan is not None, "%s: no conveyor plan" % name
+            assert self.epoch != self.layout_epoch and self.seed != self.deal_seed and 1 <= len(self.blocks) <= 8
+            bins, bpb, cap = self.plan["bins"], self.plan["bpb"], self.plan["cap"]
+            tables = orc.ldsbin_tables(self.indptr, self.indices, self.ni, bins, 10 ** 9)  # (no hot items in this layout)
+            self.rank_item = None if self.order_seed is None else np.random.RandomState(self.order_seed).permutation(
+                self.ni).astype(np.int32)
+            order = tables["rank_item"] if self.rank_item is None else self.rank_item
+            self.slot_item, self.item_slot = orc.ldsbin_layout(self.deal_seed, self.layout_epoch, bins, self.ni, order)
+            form, epoch, self.n = "ldsbin", self.epoch, self.nnz
+            kw = dict(n_bins=bins, tables=tables, deal=(self.deal_seed, self.layout_epoch), rank_item=self.rank_item,
+                      bins=[(b * bpb, (b + 1) * bpb) for b in self.blocks])
+            # all blocks' buffers as the launches find them, from the ORACLE's layout
+            self.bufs = pack(self.tables[1], self.tables[2], self.slot_item, range(self.n_blocks), bpb, cap)
+            for buf in self.bufs:
+                buf.setflags(write=False)
+        t = orc.hogwild_triplets(form, self.seed, epoch, self.s_begin, self.n, self.indptr, self.indices, self.ni,
                                  neg_pop=self.neg_pop, **kw)
+        if self.form == "conveyor":
+            t.pop("hot")  # (none is)
+            self.draws = t["draws"]
         self.trip = (t["u"], t["i"], t["j"])
         self.skipped, self.hot, self.bin, self.shared = t["skipped"], t.get("hot"), t.get("bin"), t.get("shared")
         # launch B: the Jacobi sum of every row; launch A: the float64 step of the clean triplets alone (their rows have no
@@ -230,6 +354,26 @@ def _untouched_identical(c, launch, got):
     for tab, start, g in zip("UVB", c.tables, got):
         same = (g == start).reshape(len(start), -1).all(axis=1) | (c.touches[tab] > 0)
         assert same.all(), "launch %s changed a row no triplet touches: %s" % (launch, c.describe(tab, int(np.flatnonzero(~same)[0])))
+
+
+def conveyor_tables(c, launch, bufs, U):
+    """(U, V, B) as a conveyor launch left them: `bufs` = the buffers of ALL blocks after the launch.  The buffers of the
+    blocks the launch was not given and the pad slots of those it was given must be bit-identical; what the launched
+    blocks' item slots hold goes back to the items' rows, where check_a / check_b hold every row to its rule (rows no
+    triplet touches, those beyond n_items among them: bit-identical)."""
+    bpb, cap = c.plan["bpb"], c.plan["cap"]
+    w = bpb * cap
+    for blk, (start, buf) in enumerate(zip(c.bufs, bufs)):
+        assert buf.dtype == np.float32 and buf.shape == start.shape
+        if blk not in c.blocks:
+            assert np.array_equal(start, buf), "%s, launch %s changed the buffer of block %d, which it was not given" % (c.name, launch, blk)
+            continue
+        pad = np.flatnonzero(c.slot_item[blk * w:(blk + 1) * w] < 0)
+        rows, bias = buf[:w * c.k].reshape(w, c.k)[pad], buf[w * c.k + pad]
+        assert (rows == np.float32(PAD)).all() and (bias == np.float32(PAD)).all(), "%s, launch %s changed a pad slot of block %d" % (
+            c.name, launch, blk)
+    V, B = unpack([bufs[b] for b in c.blocks], c.tables[1], c.tables[2], c.slot_item, c.blocks, bpb, cap)
+    return U, V, B
 
 
 def check_z(c, got, correct, skipped):

@@ -1,7 +1,8 @@
 """The arithmetic of the hogwild BPR kernels against the float64 step, triplet by triplet: every kernel instantiation the
 dispatchers return runs one short launch three times (tests/bpr_step_cases.py: Z at lr = 0, A at lr = 0.05 on the rows of
 clean triplets, B at lr = 2^-12 on every touched row), and the triplets of that launch are known beforehand from the CPU
-restatements of the samplers.  tests/test_bpr_step_cpu.py proves the cases fair and the checks sharp."""
+restatements of the samplers.  tests/test_bpr_step_cpu.py proves the cases fair and the checks sharp.  The conveyor's
+launches (cornac_hip_bpr_conveyor_enqueue: the rows in block buffers) run under the same three rules in a test of their own."""
 import numpy as np
 import pytest
 
@@ -24,7 +25,7 @@ def _launch(tr, c, lr):
     return tr.get_factors(), correct, skipped
 
 
-@pytest.mark.parametrize("name", bc.NAMES)
+@pytest.mark.parametrize("name", [name for name in bc.NAMES if name not in bc.CONVEYOR_NAMES])
 def test_hogwild_launch_matches_the_float64_step(oracle, name):
     cus = _lib.device_info(0)["compute_units"]
     c = bc.case(name, cus)
@@ -62,3 +63,63 @@ def test_hogwild_launch_matches_the_float64_step(oracle, name):
           "B error / tolerance U %.3g V %.3g B %.3g (C %.3g)" % (
               name, len(c.trip[0]), z["correct"], z["lo"], z["hi"], a["U"], a["V"], a["B"], bc.T_CLEAN, b["U"], b["V"], b["B"],
               bc.C[name]))
+
+
+def _conveyor_launch(tr, c, lr):
+    """one conveyor launch of the case from its start tables and start buffers: ((U, V, B), correct, skipped).  The buffers
+    of ALL blocks are on the device; the launch is given those of c.blocks, in that order."""
+    import torch
+
+    tr.set_factors(c.tables[0], None, None)
+    tr.seed_hogwild(c.seed)
+    bufs = [torch.as_tensor(b.copy()).to("cuda:0") for b in c.bufs]
+    torch.cuda.synchronize()
+    tr.conveyor_enqueue(c.epoch, c.layout_epoch, list(c.blocks), [bufs[b].data_ptr() for b in c.blocks], lr, bc.REG if lr else 0.0,
+                        c.use_bias, c.neg_population, c.flags)
+    correct, skipped = tr.sync()
+    launch = "Z" if lr == 0.0 else "A" if lr == bc.LR_A else "B"
+    return bc.conveyor_tables(c, launch, [b.cpu().numpy() for b in bufs], tr.get_user_factors()), correct, skipped
+
+
+@pytest.mark.parametrize("name", bc.CONVEYOR_NAMES)
+def test_conveyor_launch_matches_the_float64_step(oracle, name):
+    import torch
+
+    cus = _lib.device_info(0)["compute_units"]
+    c = bc.case(name, cus)
+    tr = _lib.BprTrainer(c.indptr, c.indices, c.nu, c.ni, c.nu, c.ni, c.k)
+    try:
+        got = tr.conveyor_setup(c.n_blocks, c.rank_item, c.deal_seed)
+        assert got == (c.plan["bins"], c.plan["bpb"], c.plan["cap"]), (got, c.plan)
+        # the device's layout of (deal_seed, layout_epoch) against the oracle's, from which the buffers are filled
+        slot_item = torch.full((len(c.slot_item),), -2, dtype=torch.int32, device="cuda:0")
+        item_slot = torch.full((c.ni,), -2, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        tr.conveyor_layout(c.layout_epoch, slot_item.data_ptr(), item_slot.data_ptr())
+        tr.sync()
+        assert np.array_equal(slot_item.cpu().numpy(), c.slot_item), "%s: slot_item differs from its restatement" % name
+        assert np.array_equal(item_slot.cpu().numpy(), c.item_slot), "%s: item_slot differs from its restatement" % name
+        tables, correct, skipped = _conveyor_launch(tr, c, 0.0)
+        z = bc.check_z(c, tables, correct, skipped)
+        a = bc.check_a(c, _conveyor_launch(tr, c, bc.LR_A)[0])
+        b = bc.check_b(c, _conveyor_launch(tr, c, bc.LR_B)[0])
+        assert tr.ldsbin_stats()["lock_timeouts"] == 0
+    finally:
+        tr.close()
+    print("\n%s: %d bins, %d per block, %d rows per bin, blocks %s; %d triplets (%d skipped), correct %d in [%d, %d]; A clean-row "
+          "error U %.3g V %.3g B %.3g (T_CLEAN %.3g); B error / tolerance U %.3g V %.3g B %.3g (C %.3g)" % (
+              name, got[0], got[1], got[2], list(c.blocks), len(c.trip[0]), c.skipped, z["correct"], z["lo"], z["hi"], a["U"], a["V"],
+              a["B"], bc.T_CLEAN, b["U"], b["V"], b["B"], bc.C[name]))
+
+
+def test_conveyor_setup_refuses_k_above_256():
+    rs = np.random.RandomState(0)
+    indptr = np.arange(0, 4 * 1000 + 1, 4, dtype=np.int32)
+    indices = np.sort(rs.randint(0, 8192, (1000, 4)), axis=1).astype(np.int32)
+    indices += np.arange(4, dtype=np.int32)  # (strictly ascending within a user)
+    tr = _lib.BprTrainer(indptr, indices.ravel(), 1000, 8196, 1000, 8196, 257)
+    try:
+        with pytest.raises(_lib.HipError, match="no conveyor layout"):
+            tr.conveyor_setup(4, None, 1)
+    finally:
+        tr.close()
