@@ -75,6 +75,9 @@ SYMBOLS = [
     "cornac_hip_knn_sim_get",
     "cornac_hip_knn_scorer_create", "cornac_hip_knn_scorer_destroy", "cornac_hip_knn_scorer_score_users",
     "cornac_hip_knn_scorer_score_pairs",
+    "cornac_hip_ease_create", "cornac_hip_ease_destroy", "cornac_hip_ease_gram", "cornac_hip_ease_invert",
+    "cornac_hip_ease_weights", "cornac_hip_ease_fit", "cornac_hip_ease_get_table", "cornac_hip_ease_set_table",
+    "cornac_hip_ease_score_users", "cornac_hip_ease_score_pairs",
 ]
 
 
@@ -301,6 +304,16 @@ def lib():
         L.cornac_hip_knn_scorer_destroy.argtypes = [_vp]
         L.cornac_hip_knn_scorer_score_users.argtypes = [_vp, _vp, C.c_int64, C.c_int, _vp]
         L.cornac_hip_knn_scorer_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, C.c_int, _vp]
+        L.cornac_hip_ease_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, _vp]
+        L.cornac_hip_ease_destroy.argtypes = [_vp]
+        L.cornac_hip_ease_gram.argtypes = [_vp]
+        L.cornac_hip_ease_invert.argtypes = [_vp, C.c_double]
+        L.cornac_hip_ease_weights.argtypes = [_vp, C.c_int]
+        L.cornac_hip_ease_fit.argtypes = [_vp, C.c_double, C.c_int]
+        L.cornac_hip_ease_get_table.argtypes = [_vp, _vp]
+        L.cornac_hip_ease_set_table.argtypes = [_vp, _vp]
+        L.cornac_hip_ease_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_ease_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
         _lib = L
     return _lib
 
@@ -1268,4 +1281,60 @@ class KnnScorer:
         assert len(users) == len(items)
         out = np.empty(len(users), np.float64)
         check(lib().cornac_hip_knn_scorer_score_pairs(self.h, _ptr(users), _ptr(items), len(users), int(k), _ptr(out)))
+        return out
+
+
+class EaseModel:
+    """Owner of a cornac_hip_ease_t handle: X (users x items, scipy CSR) and the dense items x items float64 table that is
+    G, then P, then B of cornac/models/ease/recom_ease.py:72-97, and the scores of :123-126 against it."""
+
+    def __init__(self, X, device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        csr = _csr_arrays(X)
+        self.h = _vp()
+        check(lib().cornac_hip_ease_create(C.byref(self.h), device, self.n_users, self.n_items, *[_ptr(a) for a in csr]))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h and lib is not None:
+            lib().cornac_hip_ease_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def gram(self):
+        check(lib().cornac_hip_ease_gram(self.h))
+
+    def invert(self, lamb):
+        check(lib().cornac_hip_ease_invert(self.h, float(lamb)))
+
+    def weights(self, posB):
+        check(lib().cornac_hip_ease_weights(self.h, int(bool(posB))))
+
+    def fit(self, lamb, posB):
+        """gram, invert, weights in one call"""
+        check(lib().cornac_hip_ease_fit(self.h, float(lamb), int(bool(posB))))
+
+    def get_table(self):
+        out = np.empty((self.n_items, self.n_items), np.float64)
+        check(lib().cornac_hip_ease_get_table(self.h, _ptr(out)))
+        return out
+
+    def set_table(self, table):
+        table = np.ascontiguousarray(table, np.float64)
+        assert table.shape == (self.n_items, self.n_items), "the table is items x items"
+        check(lib().cornac_hip_ease_set_table(self.h, _ptr(table)))
+
+    def score_users(self, users):
+        """X[users, :] . table: [n, n_items] float64"""
+        users = np.ascontiguousarray(users, np.int32)
+        out = np.empty((len(users), self.n_items), np.float64)
+        check(lib().cornac_hip_ease_score_users(self.h, _ptr(users), len(users), _ptr(out)))
+        return out
+
+    def score_pairs(self, users, items):
+        """X[users[p], :] . table[:, items[p]]: [n] float64"""
+        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
+        assert len(users) == len(items)
+        out = np.empty(len(users), np.float64)
+        check(lib().cornac_hip_ease_score_pairs(self.h, _ptr(users), _ptr(items), len(users), _ptr(out)))
         return out

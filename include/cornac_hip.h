@@ -769,6 +769,42 @@ int cornac_hip_knn_scorer_score_users(cornac_hip_knn_scorer_t h, const int32_t *
 int cornac_hip_knn_scorer_score_pairs(cornac_hip_knn_scorer_t h, const int32_t *users, const int32_t *items, int64_t n, int k,
                                       double *out);
 
+/* ------------------------------------------------------------------------- *
+ * EASE (Steck 2019), float64 throughout.
+ * Replaces: the NumPy / SciPy body of EASE.fit and EASE.score,
+ *           cornac/models/ease/recom_ease.py:72-97 and :123-126.
+ * The handle owns X = train_set.matrix on the device (CSR as given, sorted indices without repeats, finite values --
+ * all checked -- and its CSC) and ONE dense [n_items x n_items] row-major table, which is G, then P, then B, in place.
+ * ------------------------------------------------------------------------- */
+typedef struct cornac_hip_ease *cornac_hip_ease_t;
+
+/* Fails with CORNAC_HIP_ERR_HIP and a message stating the bytes wanted when the table cannot be allocated.  The table
+ * starts as zeros. */
+int cornac_hip_ease_create(cornac_hip_ease_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                           const int32_t *indices, const double *data);
+int cornac_hip_ease_destroy(cornac_hip_ease_t h);
+/* table <- X^T X (recom_ease.py:78): G[i, j] = sum over the users in ascending order of x_ui * x_uj, product and sum rounded
+ * separately -- the bits of SciPy's sparse product.  A repeated run gives the same bits. */
+int cornac_hip_ease_gram(cornac_hip_ease_t h);
+/* table <- inv(table + lamb I) (recom_ease.py:80-84) by blocked Gauss-Jordan without pivoting, block 64, every sum in
+ * one fixed order.  lamb must be > 0 (a departure from the reference, which hands a singular G to NumPy).  A pivot that
+ * is not a positive finite number makes the call return CORNAC_HIP_ERR_INVALID with "... not positive definite at block
+ * N" once the sweep is through; the table then holds no inverse, and the handle stays usable. */
+int cornac_hip_ease_invert(cornac_hip_ease_t h, double lamb);
+/* table <- B (recom_ease.py:86-92): column j divided by -P_jj, the diagonal 0, and with pos_b every entry that is not
+ * above 0 replaced by +0.0 */
+int cornac_hip_ease_weights(cornac_hip_ease_t h, int pos_b);
+/* gram, invert, weights in one call: the same bits as the three calls */
+int cornac_hip_ease_fit(cornac_hip_ease_t h, double lamb, int pos_b);
+/* the table to / from table[n_items * n_items] on the host */
+int cornac_hip_ease_get_table(cornac_hip_ease_t h, double *table);
+int cornac_hip_ease_set_table(cornac_hip_ease_t h, const double *table);
+/* out[n x n_items] = X[users[b], :] . table (recom_ease.py:124): y = 0, then y += x * table[j, :] over the user's entries in
+ * ascending item order, product and sum rounded separately -- the bits of SciPy's csr . dense */
+int cornac_hip_ease_score_users(cornac_hip_ease_t h, const int32_t *users, int64_t n, double *out);
+/* out[n]: X[users[p], :] . table[:, items[p]] (recom_ease.py:126); the bits of the matching score_users entry */
+int cornac_hip_ease_score_pairs(cornac_hip_ease_t h, const int32_t *users, const int32_t *items, int64_t n, double *out);
+
 #ifdef __cplusplus
 }
 #endif
