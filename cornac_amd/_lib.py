@@ -78,6 +78,9 @@ SYMBOLS = [
     "cornac_hip_ease_create", "cornac_hip_ease_destroy", "cornac_hip_ease_gram", "cornac_hip_ease_invert",
     "cornac_hip_ease_weights", "cornac_hip_ease_fit", "cornac_hip_ease_get_table", "cornac_hip_ease_set_table",
     "cornac_hip_ease_score_users", "cornac_hip_ease_score_pairs",
+    "cornac_hip_vaecf_create", "cornac_hip_vaecf_destroy", "cornac_hip_vaecf_set_params", "cornac_hip_vaecf_get_params",
+    "cornac_hip_vaecf_get_state", "cornac_hip_vaecf_reset_optimizer", "cornac_hip_vaecf_fit_epoch",
+    "cornac_hip_vaecf_encode_users", "cornac_hip_vaecf_score_users", "cornac_hip_vaecf_score_pairs",
 ]
 
 
@@ -314,6 +317,17 @@ def lib():
         L.cornac_hip_ease_set_table.argtypes = [_vp, _vp]
         L.cornac_hip_ease_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
         L.cornac_hip_ease_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_vaecf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int]
+        L.cornac_hip_vaecf_destroy.argtypes = [_vp]
+        L.cornac_hip_vaecf_set_params.argtypes = [_vp, _vp]
+        L.cornac_hip_vaecf_get_params.argtypes = [_vp, _vp]
+        L.cornac_hip_vaecf_get_state.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_vaecf_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_vaecf_fit_epoch.argtypes = [_vp, C.c_int64, C.c_float, C.c_float, _vp, C.c_uint64, C.POINTER(C.c_double), _vp]
+        L.cornac_hip_vaecf_encode_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_vaecf_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_vaecf_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
         _lib = L
     return _lib
 
@@ -1337,4 +1351,94 @@ class EaseModel:
         assert len(users) == len(items)
         out = np.empty(len(users), np.float64)
         check(lib().cornac_hip_ease_score_pairs(self.h, _ptr(users), _ptr(items), len(users), _ptr(out)))
+        return out
+
+
+class VaecfModel:
+    """Owner of a cornac_hip_vaecf_t handle: the binarised training rows, the ten tables of the reference's VAE
+    (cornac/models/vaecf/vaecf.py:37-64) with Adam's moments and step counter, the epoch of vaecf.py:127-144 and the scores
+    of recom_vaecf.py:193-202.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
+    NAMES = ("encoder.fc0.weight", "encoder.fc0.bias", "enc_mu.weight", "enc_mu.bias", "enc_logvar.weight", "enc_logvar.bias",
+             "decoder.fc0.weight", "decoder.fc0.bias", "decoder.fc1.weight", "decoder.fc1.bias")
+    ACTS = ("tanh", "sigmoid", "relu", "relu6", "elu")
+    LIKELIHOODS = ("mult", "bern", "gaus", "pois")
+
+    @staticmethod
+    def shapes(n_items, k, h):
+        return dict(zip(VaecfModel.NAMES, ((h, n_items), (h,), (k, h), (k,), (k, h), (k,), (h, k), (h,), (n_items, h), (n_items,))))
+
+    def __init__(self, X, k, h, act_fn="tanh", likelihood="mult", device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.k, self.h = int(k), int(h)
+        indptr, indices, _ = _csr_arrays(X)
+        self.h_ = _vp()
+        check(lib().cornac_hip_vaecf_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
+                                            self.k, self.h, self.ACTS.index(act_fn), self.LIKELIHOODS.index(likelihood)))
+
+    def close(self):
+        if getattr(self, "h_", None) is not None and self.h_ and lib is not None:
+            lib().cornac_hip_vaecf_destroy(self.h_)
+            self.h_ = None
+
+    __del__ = close
+
+    def _empty(self):
+        sh = self.shapes(self.n_items, self.k, self.h)
+        return {n: np.empty(sh[n], np.float32) for n in self.NAMES}
+
+    def _pointers(self, tables):
+        return (_vp * 10)(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.NAMES])
+
+    def set_params(self, params):
+        sh = self.shapes(self.n_items, self.k, self.h)
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
+        check(lib().cornac_hip_vaecf_set_params(self.h_, self._pointers(tables)))
+
+    def get_params(self):
+        out = self._empty()
+        check(lib().cornac_hip_vaecf_get_params(self.h_, self._pointers(out)))
+        return out
+
+    def get_state(self):
+        """(m, v, t): Adam's exp_avg and exp_avg_sq per table, and its step counter"""
+        m, v, t = self._empty(), self._empty(), C.c_int64()
+        check(lib().cornac_hip_vaecf_get_state(self.h_, self._pointers(m), self._pointers(v), C.byref(t)))
+        return m, v, int(t.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_vaecf_reset_optimizer(self.h_))
+
+    def fit_epoch(self, batch_size, lr, beta, eps=None, seed=0):
+        """one epoch; eps [n_users, k] is the noise (None: the device generator under `seed`).  Returns (the sum of the
+        steps' batch-mean losses, the per-step losses)."""
+        if eps is not None:
+            eps = np.ascontiguousarray(eps, np.float32)
+            assert eps.shape == (self.n_users, self.k)
+        steps = np.zeros(max(1, -(-self.n_users // max(int(batch_size), 1))), np.float64)
+        total = C.c_double()
+        check(lib().cornac_hip_vaecf_fit_epoch(self.h_, int(batch_size), float(lr), float(beta), _ptr(eps),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(total), _ptr(steps)))
+        return float(total.value), steps
+
+    def encode_users(self, users):
+        """h2 at z = mu: [n, h] float32"""
+        users = np.ascontiguousarray(users, np.int32)
+        out = np.empty((len(users), self.h), np.float32)
+        check(lib().cornac_hip_vaecf_encode_users(self.h_, _ptr(users), len(users), _ptr(out)))
+        return out
+
+    def score_users(self, users):
+        """decode(mu(x_u)): [n, n_items] float32"""
+        users = np.ascontiguousarray(users, np.int32)
+        out = np.empty((len(users), self.n_items), np.float32)
+        check(lib().cornac_hip_vaecf_score_users(self.h_, _ptr(users), len(users), _ptr(out)))
+        return out
+
+    def score_pairs(self, users, items):
+        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
+        assert len(users) == len(items)
+        out = np.empty(len(users), np.float32)
+        check(lib().cornac_hip_vaecf_score_pairs(self.h_, _ptr(users), _ptr(items), len(users), _ptr(out)))
         return out

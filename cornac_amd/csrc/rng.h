@@ -71,8 +71,8 @@ __device__ inline uint32_t mt_temper(uint32_t y) {
     return y;
 }
 
-// grid = number of streams (one workgroup each), block = MT_THREADS
-__global__ __launch_bounds__(MT_THREADS) void mt19937_draw_kernel(const MtStreamParams *params) {
+// grid = number of streams (one workgroup each), block = MT_THREADS (static: this header is included by several sources)
+static __global__ __launch_bounds__(MT_THREADS) void mt19937_draw_kernel(const MtStreamParams *params) {
     const MtStreamParams P = params[blockIdx.x];
     __shared__ uint32_t st[2][MT_N];
     __shared__ int wave_cnt[MT_THREADS / 64];

@@ -805,6 +805,51 @@ int cornac_hip_ease_score_users(cornac_hip_ease_t h, const int32_t *users, int64
 /* out[n]: X[users[p], :] . table[:, items[p]] (recom_ease.py:126); the bits of the matching score_users entry */
 int cornac_hip_ease_score_pairs(cornac_hip_ease_t h, const int32_t *users, const int32_t *items, int64_t n, double *out);
 
+/* ------------------------------------------------------------------------- *
+ * VAECF (Liang et al. 2018, "Mult-VAE"), float32 throughout, one hidden layer.
+ * Replaces: VAE.forward / VAE.loss / learn, cornac/models/vaecf/vaecf.py:37-149, and VAECF.score,
+ *           cornac/models/vaecf/recom_vaecf.py:193-202.
+ * The handle owns the binarised training CSR (sorted indices without repeats, checked; stored values are never read:
+ * every stored entry counts as 1, as `u_batch.data = ones` does at vaecf.py:131), its CSC, the ten tables with Adam's m
+ * and v, and Adam's step counter t, which persist across calls.  Tables are passed as arrays of ten pointers in the order
+ * and with the shapes of the reference's state_dict:
+ *   0 encoder.fc0.weight [h x I]   1 encoder.fc0.bias [h]   2 enc_mu.weight [k x h]      3 enc_mu.bias [k]
+ *   4 enc_logvar.weight [k x h]    5 enc_logvar.bias [k]    6 decoder.fc0.weight [h x k] 7 decoder.fc0.bias [h]
+ *   8 decoder.fc1.weight [I x h]   9 decoder.fc1.bias [I]
+ * (the device keeps table 0 transposed).  A NULL entry skips its table.
+ * act: 0 tanh, 1 sigmoid, 2 relu, 3 relu6, 4 elu (alpha 1).  likelihood: 0 mult, 1 bern, 2 gaus, 3 pois.
+ * Supported: 1 <= k <= 256, 1 <= h <= 1024, 1 <= batch_size <= 1024; anything else is CORNAC_HIP_ERR_INVALID with a
+ * message naming the limit.  No float atomics; every sum has one fixed order: the same inputs give the same bits.
+ * ------------------------------------------------------------------------- */
+typedef struct cornac_hip_vaecf *cornac_hip_vaecf_t;
+
+/* vaecf.py:38-64 (the model's shape) and :130-133 (the batch rows, here never densified); all tables start as zeros */
+int cornac_hip_vaecf_create(cornac_hip_vaecf_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                            const int32_t *indices, int k, int h, int act, int likelihood);
+int cornac_hip_vaecf_destroy(cornac_hip_vaecf_t h);
+/* the ten tables from / to the host (state_dict of vaecf.py:37-64) */
+int cornac_hip_vaecf_set_params(cornac_hip_vaecf_t h, const float *const *tables);
+int cornac_hip_vaecf_get_params(cornac_hip_vaecf_t h, float *const *tables);
+/* Adam's exp_avg (m) and exp_avg_sq (v), in the tables' shapes, and its step counter (vaecf.py:120); NULL skips */
+int cornac_hip_vaecf_get_state(cornac_hip_vaecf_t h, float *const *m, float *const *v, int64_t *t);
+/* m = v = 0, t = 0: what a new torch.optim.Adam (vaecf.py:120, once per learn()) starts from */
+int cornac_hip_vaecf_reset_optimizer(cornac_hip_vaecf_t h);
+/* One epoch of vaecf.py:127-144: ceil(n_users / batch_size) steps over consecutive user ranges (user_iter without
+ * shuffling), each a forward, a backward and torch.optim.Adam's dense sweep (betas 0.9 / 0.999, eps 1e-8) over every
+ * table, enqueued from this one call with one synchronise at the end.  eps [n_users x k] is the noise of
+ * reparameterize() (vaecf.py:79), row = user; NULL draws it on the device (Philox keyed by seed, step, user, factor).
+ * loss_sum: the sum over the steps of the batch-mean loss (`sum_loss` of vaecf.py:143); step_loss [steps]: each of them.
+ * Either may be NULL. */
+int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float lr, float beta, const float *eps, uint64_t seed,
+                               double *loss_sum, double *step_loss);
+/* h2_out [n x h]: the decoder's hidden layer at z = mu(x_u) (recom_vaecf.py:194-196 and the first half of decode):
+ * score = softmax / sigmoid of c1 + <h2(u), D1[i]>, so (h2, D1, c1) are a factor model's ranking tables */
+int cornac_hip_vaecf_encode_users(cornac_hip_vaecf_t h, const int32_t *users, int64_t n, float *h2_out);
+/* out [n x n_items] = decode(mu(x_u)) (recom_vaecf.py:193-197); score_pairs: out[p] is the entry items[p] of users[p]'s
+ * row (recom_vaecf.py:198-202), the bits of the matching score_users entry */
+int cornac_hip_vaecf_score_users(cornac_hip_vaecf_t h, const int32_t *users, int64_t n, float *out);
+int cornac_hip_vaecf_score_pairs(cornac_hip_vaecf_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif
