@@ -383,8 +383,35 @@ def _f32c(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32)
 
 
-class BprTrainer:
+class _HandleOwner:
+    """Owner of one native handle, kept in the attribute `_HANDLE` names and released by the library's `_DESTROY`.  close()
+    may be called twice, after an __init__ that failed before the handle existed, and while the interpreter shuts down."""
+    _DESTROY = None
+    _HANDLE = "h"
+
+    def close(self):
+        h = getattr(self, self._HANDLE, None)
+        if h is not None and h and lib is not None:
+            getattr(lib(), self._DESTROY)(h)
+            setattr(self, self._HANDLE, None)
+
+    __del__ = close
+
+
+def _score_by_ids(symbol, h, dtype, users, items=None, width=None, extra=()):
+    """`symbol`(h, users[, items], n, *extra, out) over contiguous int32 ids: out is [n, width] (a row per user) or, for
+    pairs, [n]"""
+    ids = [np.ascontiguousarray(users, np.int32)] + ([] if items is None else [np.ascontiguousarray(items, np.int32)])
+    n = len(ids[0])
+    assert all(len(a) == n for a in ids)
+    out = np.empty(n if width is None else (n, width), dtype)
+    check(getattr(lib(), symbol)(h, *[_ptr(a) for a in ids], n, *extra, _ptr(out)))
+    return out
+
+
+class BprTrainer(_HandleOwner):
     """Thin owner of a cornac_hip_bpr_t handle."""
+    _DESTROY = "cornac_hip_bpr_destroy"
 
     def __init__(self, indptr, indices, n_users, n_items, total_users, total_items, k, device=0):
         self.indptr = np.ascontiguousarray(indptr, np.int32)
@@ -396,13 +423,6 @@ class BprTrainer:
         self.h = _vp()
         check(lib().cornac_hip_bpr_create(C.byref(self.h), device, n_users, n_items, total_users, total_items, k,
                                           self.indptr, self.indices, self.nnz))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_bpr_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def set_factors(self, U=None, V=None, B=None):
         U, V, B = _f32c(U), _f32c(V), _f32c(B)
@@ -730,7 +750,9 @@ class BprTrainer:
         return {"sampler_ms": t[0], "schedule_ms": t[1], "sgd_ms": t[2], "total_ms": t[3]}
 
 
-class MfTrainer:
+class MfTrainer(_HandleOwner):
+    _DESTROY = "cornac_hip_mf_destroy"
+
     def __init__(self, rid, cid, val, n_users, n_items, k, device=0):
         self.rid = np.ascontiguousarray(rid, np.int64)
         self.cid = np.ascontiguousarray(cid, np.int64)
@@ -740,13 +762,6 @@ class MfTrainer:
         check(lib().cornac_hip_mf_create(C.byref(self.h), device, n_users, n_items, k, self.rid, self.cid, self.val,
                                          len(self.val)))
         self.device, self._stream = int(device), None
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_mf_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def set_factors(self, U=None, V=None, Bu=None, Bi=None):
         U, V, Bu, Bi = _f32c(U), _f32c(V), _f32c(Bu), _f32c(Bi)
@@ -985,7 +1000,9 @@ def mf_fit_sgd(rid, cid, val, U, V, Bu, Bi, lr, reg, mu, max_iter, use_bias, ear
     return loss[:n.value]
 
 
-class Scorer:
+class Scorer(_HandleOwner):
+    _DESTROY = "cornac_hip_scorer_destroy"
+
     def __init__(self, U, V, item_base=None, user_base=None, device=0):
         U, V = _f32c(U), _f32c(V)
         self.n_users, self.k = U.shape
@@ -997,13 +1014,6 @@ class Scorer:
     def set(self, U, V, item_base=None, user_base=None):
         ib, ub = _f32c(item_base), _f32c(user_base)
         check(lib().cornac_hip_scorer_set(self.h, _f32c(U), _f32c(V), _ptr(ib), _ptr(ub)))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_scorer_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def score_user(self, user):
         out = np.empty(self.n_items, np.float32)
@@ -1111,7 +1121,8 @@ class Scorer:
         return ms.value
 
 
-class VbprTrainer:
+class VbprTrainer(_HandleOwner):
+    _DESTROY = "cornac_hip_vbpr_destroy"
     NAMES = ("Bi", "Gu", "Gi", "Tu", "E", "Bp")
 
     def __init__(self, features, n_users, n_items, k, k2, device=0):
@@ -1120,13 +1131,6 @@ class VbprTrainer:
         self.dims = dict(n_users=int(n_users), n_items=int(n_items), k=int(k), k2=int(k2), n_feat=self.F.shape[1])
         self.h = _vp()
         check(lib().cornac_hip_vbpr_create(C.byref(self.h), device, n_users, n_items, k, k2, self.F.shape[1], self.F))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_vbpr_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def _shapes(self):
         d = self.dims
@@ -1161,8 +1165,9 @@ class VbprTrainer:
         return th, vb
 
 
-class WmfTrainer:
+class WmfTrainer(_HandleOwner):
     """Resident WMF trainer: CSC rating matrix, U/V and the Adam state live on the device."""
+    _DESTROY = "cornac_hip_wmf_destroy"
 
     def __init__(self, csc, k, device=0):
         csc = csc.tocsc()
@@ -1175,13 +1180,6 @@ class WmfTrainer:
         check(lib().cornac_hip_wmf_create(C.byref(self.h), device, self.n_users, self.n_items, self.k, self._indptr,
                                           self._rows if len(self._rows) else np.zeros(1, np.int32),
                                           self._vals if len(self._vals) else np.zeros(1, np.float32), len(self._vals)))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_wmf_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def set_factors(self, U, V):
         U = np.ascontiguousarray(np.asarray(U, np.float32).reshape(self.n_users, self.k))
@@ -1229,9 +1227,10 @@ def _csr_arrays(mat):
             np.ascontiguousarray(mat.data, np.float64))
 
 
-class KnnSimilarity:
+class KnnSimilarity(_HandleOwner):
     """Owner of a cornac_hip_knn_sim_t handle: `compute_similarity` of cornac/models/knn/similarity.pyx:51-105 over the rows
     of a scipy CSR, as a scipy CSR of float64."""
+    _DESTROY = "cornac_hip_knn_sim_destroy"
 
     def __init__(self, W, device=0):
         self.shape = tuple(int(x) for x in W.shape)
@@ -1239,13 +1238,6 @@ class KnnSimilarity:
         self.h = _vp()
         check(lib().cornac_hip_knn_sim_create(C.byref(self.h), device, self.shape[0], self.shape[1],
                                               *[_ptr(a) for a in self._csr]))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_knn_sim_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def run(self, rows_per_pass=0):
         """rows_per_pass: rows whose accumulators are held at once (0: chosen from the free device memory)"""
@@ -1260,9 +1252,10 @@ class KnnSimilarity:
         return sp.csr_matrix((data, indices, indptr.astype(np.int32) if nnz.value < 2 ** 31 else indptr), shape=(n, n))
 
 
-class KnnScorer:
+class KnnScorer(_HandleOwner):
     """Owner of a cornac_hip_knn_scorer_t handle: `compute_score` / `compute_score_single` (similarity.pyx:108-201) for the
     neighbour table N [n_items x n_neighbours] and the query table Q [n_users x n_neighbours], both scipy CSR."""
+    _DESTROY = "cornac_hip_knn_scorer_destroy"
 
     MAX_K = KNN_MAX_K
 
@@ -1275,45 +1268,25 @@ class KnnScorer:
         check(lib().cornac_hip_knn_scorer_create(C.byref(self.h), device, self.n_items, self.n_neighbours, self.n_users,
                                                  *[_ptr(a) for a in n + q], int(bool(user_mode))))
 
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_knn_scorer_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
     def score_users(self, users, k):
         """weighted averages [n, n_items] float64"""
-        users = np.ascontiguousarray(users, np.int32)
-        out = np.empty((len(users), self.n_items), np.float64)
-        check(lib().cornac_hip_knn_scorer_score_users(self.h, _ptr(users), len(users), int(k), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_knn_scorer_score_users", self.h, np.float64, users, width=self.n_items, extra=(int(k),))
 
     def score_pairs(self, users, items, k):
         """weighted averages [n] float64 for the pairs (users[p], items[p])"""
-        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
-        assert len(users) == len(items)
-        out = np.empty(len(users), np.float64)
-        check(lib().cornac_hip_knn_scorer_score_pairs(self.h, _ptr(users), _ptr(items), len(users), int(k), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_knn_scorer_score_pairs", self.h, np.float64, users, items, extra=(int(k),))
 
 
-class EaseModel:
+class EaseModel(_HandleOwner):
     """Owner of a cornac_hip_ease_t handle: X (users x items, scipy CSR) and the dense items x items float64 table that is
     G, then P, then B of cornac/models/ease/recom_ease.py:72-97, and the scores of :123-126 against it."""
+    _DESTROY = "cornac_hip_ease_destroy"
 
     def __init__(self, X, device=0):
         self.n_users, self.n_items = (int(x) for x in X.shape)
         csr = _csr_arrays(X)
         self.h = _vp()
         check(lib().cornac_hip_ease_create(C.byref(self.h), device, self.n_users, self.n_items, *[_ptr(a) for a in csr]))
-
-    def close(self):
-        if getattr(self, "h", None) is not None and self.h and lib is not None:
-            lib().cornac_hip_ease_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def gram(self):
         check(lib().cornac_hip_ease_gram(self.h))
@@ -1340,24 +1313,19 @@ class EaseModel:
 
     def score_users(self, users):
         """X[users, :] . table: [n, n_items] float64"""
-        users = np.ascontiguousarray(users, np.int32)
-        out = np.empty((len(users), self.n_items), np.float64)
-        check(lib().cornac_hip_ease_score_users(self.h, _ptr(users), len(users), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_ease_score_users", self.h, np.float64, users, width=self.n_items)
 
     def score_pairs(self, users, items):
         """X[users[p], :] . table[:, items[p]]: [n] float64"""
-        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
-        assert len(users) == len(items)
-        out = np.empty(len(users), np.float64)
-        check(lib().cornac_hip_ease_score_pairs(self.h, _ptr(users), _ptr(items), len(users), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_ease_score_pairs", self.h, np.float64, users, items)
 
 
-class VaecfModel:
+class VaecfModel(_HandleOwner):
     """Owner of a cornac_hip_vaecf_t handle: the binarised training rows, the ten tables of the reference's VAE
     (cornac/models/vaecf/vaecf.py:37-64) with Adam's moments and step counter, the epoch of vaecf.py:127-144 and the scores
     of recom_vaecf.py:193-202.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
+    _DESTROY = "cornac_hip_vaecf_destroy"
+    _HANDLE = "h_"   # (`h` is the hidden size here)
     NAMES = ("encoder.fc0.weight", "encoder.fc0.bias", "enc_mu.weight", "enc_mu.bias", "enc_logvar.weight", "enc_logvar.bias",
              "decoder.fc0.weight", "decoder.fc0.bias", "decoder.fc1.weight", "decoder.fc1.bias")
     ACTS = ("tanh", "sigmoid", "relu", "relu6", "elu")
@@ -1374,13 +1342,6 @@ class VaecfModel:
         self.h_ = _vp()
         check(lib().cornac_hip_vaecf_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                             self.k, self.h, self.ACTS.index(act_fn), self.LIKELIHOODS.index(likelihood)))
-
-    def close(self):
-        if getattr(self, "h_", None) is not None and self.h_ and lib is not None:
-            lib().cornac_hip_vaecf_destroy(self.h_)
-            self.h_ = None
-
-    __del__ = close
 
     def _empty(self):
         sh = self.shapes(self.n_items, self.k, self.h)
@@ -1424,21 +1385,11 @@ class VaecfModel:
 
     def encode_users(self, users):
         """h2 at z = mu: [n, h] float32"""
-        users = np.ascontiguousarray(users, np.int32)
-        out = np.empty((len(users), self.h), np.float32)
-        check(lib().cornac_hip_vaecf_encode_users(self.h_, _ptr(users), len(users), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_vaecf_encode_users", self.h_, np.float32, users, width=self.h)
 
     def score_users(self, users):
         """decode(mu(x_u)): [n, n_items] float32"""
-        users = np.ascontiguousarray(users, np.int32)
-        out = np.empty((len(users), self.n_items), np.float32)
-        check(lib().cornac_hip_vaecf_score_users(self.h_, _ptr(users), len(users), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_vaecf_score_users", self.h_, np.float32, users, width=self.n_items)
 
     def score_pairs(self, users, items):
-        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
-        assert len(users) == len(items)
-        out = np.empty(len(users), np.float32)
-        check(lib().cornac_hip_vaecf_score_pairs(self.h_, _ptr(users), _ptr(items), len(users), _ptr(out)))
-        return out
+        return _score_by_ids("cornac_hip_vaecf_score_pairs", self.h_, np.float32, users, items)

@@ -22,10 +22,7 @@
 // Scoring.  One thread per (user, output item), consecutive threads on consecutive items, so the rows of B are read
 // coalesced: y = 0, then y += x * B[j, :] over the user's entries in ascending item order, * and + rounded on their own:
 // the order of SciPy's csr . dense, for the full row and for the single column.
-#include "common.h"
-
-#include <algorithm>
-#include <cmath>
+#include "sparse_model.h"
 
 namespace chip {
 namespace {
@@ -39,20 +36,8 @@ static_assert(kEaseBlock == 4 * kEaseNb && kEaseTileM == kEaseNb && kEaseNb % kE
 static_assert(kEaseBlock == (kEaseTileM / 4) * (kEaseTileN / 8) && (kEaseKc * kEaseTileM) % kEaseBlock == 0,
               "the update's 4 x 8 outputs per thread");
 
-template <class T>
-void ease_alloc(DevBuf<T> &b, size_t count, const char *what) {
-    b.release();
-    if (!count) return;
-    T *p = nullptr;
-    const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail(CORNAC_HIP_ERR_HIP, "EASE: cannot allocate %zu bytes of device memory for %s (%s)", count * sizeof(T), what,
-             hipGetErrorString(e));
-    }
-    b.p = p;
-    b.n = count;
-}
+// scoring chunks: at most kEaseScoreBytes of scores and kEaseMaxUsers users (the grid's y) per users call
+constexpr int64_t kEaseScoreBytes = 256ll << 20, kEaseMaxUsers = 65535, kEaseMaxPairs = 1 << 20;
 
 // ---- Gram ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kEaseBlock) void ease_gram_kernel(
@@ -288,20 +273,12 @@ __global__ void ease_score_pairs_kernel(const int64_t *__restrict__ row_ptr, con
 
 using namespace chip;
 
-struct cornac_hip_ease {
-    int device = 0;
+struct cornac_hip_ease : ModelHandle {
     int64_t n_users = 0, n_items = 0;
-    hipStream_t stream = nullptr;
-    DevBuf<int64_t> row_ptr, col_ptr;
-    DevBuf<int32_t> row_idx, col_idx, users, items;
-    DevBuf<double> row_val, col_val, table, diag, D, out;
+    DevCsr rows, cols;   // X and its transpose
+    DevBuf<double> table, diag, D, out;
     DevBuf<int> flag;
 };
-
-static void ease_check(cornac_hip_ease_t h) {
-    REQUIRE(h != nullptr, "EASE handle is NULL");
-    HIP_CHECK(hipSetDevice(h->device));
-}
 
 int cornac_hip_ease_create(cornac_hip_ease_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
                            const int32_t *indices, const double *data) {
@@ -310,37 +287,11 @@ int cornac_hip_ease_create(cornac_hip_ease_t *out, int device, int64_t n_users, 
         *out = nullptr;
         REQUIRE(n_users > 0 && n_items > 0, "EASE: sizes must be positive");
         REQUIRE(n_users < (1ll << 31) && n_items < (1ll << 31), "EASE: user and item counts must fit int32");
-        REQUIRE(indptr != nullptr, "EASE: indptr is NULL");
-        REQUIRE(indptr[0] == 0, "EASE: indptr does not start at 0");
-        for (int64_t u = 0; u < n_users; ++u) REQUIRE(indptr[u] <= indptr[u + 1], "EASE: indptr is not monotone");
-        const int64_t nnz = indptr[n_users];
-        REQUIRE(nnz == 0 || (indices && data), "EASE: indices / data are NULL");
-        for (int64_t u = 0; u < n_users; ++u)
-            for (int64_t e = indptr[u]; e < indptr[u + 1]; ++e) {
-                REQUIRE(indices[e] >= 0 && indices[e] < n_items, "EASE: item index out of range in row %lld", (long long)u);
-                REQUIRE(e == indptr[u] || indices[e - 1] < indices[e], "EASE: X needs sorted indices without repeats (row %lld)",
-                        (long long)u);
-                REQUIRE(std::isfinite(data[e]), "EASE: the rating of user %lld, item %d is not finite", (long long)u, indices[e]);
-            }
-        // the items' entries, users ascending: a counting sort
-        std::vector<int64_t> cptr((size_t)n_items + 1, 0);
-        for (int64_t e = 0; e < nnz; ++e) ++cptr[(size_t)indices[e] + 1];
-        for (int64_t c = 0; c < n_items; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
-        std::vector<int32_t> cidx((size_t)nnz);
-        std::vector<double> cval((size_t)nnz);
-        {
-            std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
-            for (int64_t u = 0; u < n_users; ++u)
-                for (int64_t e = indptr[u]; e < indptr[u + 1]; ++e) {
-                    const int64_t d = fill[(size_t)indices[e]]++;
-                    cidx[(size_t)d] = (int32_t)u;
-                    cval[(size_t)d] = data[e];
-                }
-        }
-        use_device(device);
+        check_csr("EASE", "X", n_users, n_items, indptr, indices, data, kCsrFiniteValues);
+        const HostCsr t = transpose_csr(n_users, n_items, indptr, indices, data);   // the items' entries, users ascending
         std::unique_ptr<cornac_hip_ease> h(new cornac_hip_ease());
-        h->device = device; h->n_users = n_users; h->n_items = n_items;
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        h->open(device);
+        h->n_users = n_users; h->n_items = n_items;
         {
             // a table beyond the device's whole memory is refused before the allocator is asked
             size_t free_b = 0, total_b = 0;
@@ -350,41 +301,23 @@ int cornac_hip_ease_create(cornac_hip_ease_t *out, int device, int64_t n_users, 
                 fail(CORNAC_HIP_ERR_HIP, "EASE: cannot allocate %zu bytes of device memory for the item-item table (the device has %zu)",
                      want, total_b);
         }
-        ease_alloc(h->table, (size_t)n_items * (size_t)n_items, "the item-item table");
-        ease_alloc(h->row_ptr, (size_t)n_users + 1, "X's row pointers");
-        ease_alloc(h->col_ptr, (size_t)n_items + 1, "X's column pointers");
-        ease_alloc(h->row_idx, (size_t)nnz, "X's indices");
-        ease_alloc(h->col_idx, (size_t)nnz, "X's transposed indices");
-        ease_alloc(h->row_val, (size_t)nnz, "X's values");
-        ease_alloc(h->col_val, (size_t)nnz, "X's transposed values");
-        ease_alloc(h->diag, (size_t)n_items, "the diagonal");
-        ease_alloc(h->D, (size_t)kEaseNb * kEaseNb, "the pivot block");
-        ease_alloc(h->flag, 1, "the status flag");
+        alloc_named(h->table, (size_t)n_items * (size_t)n_items, "EASE", "the item-item table");
+        alloc_named(h->diag, (size_t)n_items, "EASE", "the diagonal");
+        alloc_named(h->D, (size_t)kEaseNb * kEaseNb, "EASE", "the pivot block");
+        alloc_named(h->flag, 1, "EASE", "the status flag");
         HIP_CHECK(hipMemsetAsync(h->table.p, 0, h->table.n * sizeof(double), h->stream));
-        h->row_ptr.upload(indptr, (size_t)n_users + 1, h->stream);
-        h->col_ptr.upload(cptr.data(), (size_t)n_items + 1, h->stream);
-        if (nnz) {
-            h->row_idx.upload(indices, (size_t)nnz, h->stream);
-            h->row_val.upload(data, (size_t)nnz, h->stream);
-            h->col_idx.upload(cidx.data(), (size_t)nnz, h->stream);
-            h->col_val.upload(cval.data(), (size_t)nnz, h->stream);
-        }
+        h->rows.upload("EASE", "X", n_users, indptr, indices, data, h->stream);
+        h->cols.upload("EASE", "X transposed", t, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         *out = h.release();
     });
 }
 
-int cornac_hip_ease_destroy(cornac_hip_ease_t h) {
-    if (!h) return CORNAC_HIP_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    delete h;
-    return CORNAC_HIP_OK;
-}
+int cornac_hip_ease_destroy(cornac_hip_ease_t h) { return destroy_handle(h); }
 
 static void ease_gram(cornac_hip_ease_t h) {
     ease_gram_kernel<<<dim3((unsigned)h->n_items), kEaseBlock, 0, h->stream>>>(
-        h->row_ptr.p, h->row_idx.p, h->row_val.p, h->col_ptr.p, h->col_idx.p, h->col_val.p, h->n_items, h->table.p);
+        h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->cols.ptr.p, h->cols.idx.p, h->cols.val.p, h->n_items, h->table.p);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -421,7 +354,7 @@ static void ease_weights(cornac_hip_ease_t h, int pos_b) {
 
 int cornac_hip_ease_gram(cornac_hip_ease_t h) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         ease_gram(h);
         HIP_CHECK(hipStreamSynchronize(h->stream));
     });
@@ -429,14 +362,14 @@ int cornac_hip_ease_gram(cornac_hip_ease_t h) {
 
 int cornac_hip_ease_invert(cornac_hip_ease_t h, double lamb) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         ease_invert(h, lamb);
     });
 }
 
 int cornac_hip_ease_weights(cornac_hip_ease_t h, int pos_b) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         ease_weights(h, pos_b);
         HIP_CHECK(hipStreamSynchronize(h->stream));
     });
@@ -444,7 +377,7 @@ int cornac_hip_ease_weights(cornac_hip_ease_t h, int pos_b) {
 
 int cornac_hip_ease_fit(cornac_hip_ease_t h, double lamb, int pos_b) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         REQUIRE(lamb > 0.0 && std::isfinite(lamb), "EASE: lamb must be a positive finite number, got %g", lamb);
         ease_gram(h);
         ease_invert(h, lamb);
@@ -455,7 +388,7 @@ int cornac_hip_ease_fit(cornac_hip_ease_t h, double lamb, int pos_b) {
 
 int cornac_hip_ease_get_table(cornac_hip_ease_t h, double *table) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         REQUIRE(table != nullptr, "EASE: table pointer is NULL");
         h->table.download(table, h->table.n, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -464,43 +397,33 @@ int cornac_hip_ease_get_table(cornac_hip_ease_t h, double *table) {
 
 int cornac_hip_ease_set_table(cornac_hip_ease_t h, const double *table) {
     return guarded([&] {
-        ease_check(h);
+        check_handle(h, "EASE handle");
         REQUIRE(table != nullptr, "EASE: table pointer is NULL");
         h->table.upload(table, h->table.n, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
     });
 }
 
-// users[0..n) (and items[0..n) for pairs) in chunks whose scores take at most 256 MiB on the device
+// users[0..n) (and items[0..n) for pairs) in chunks whose scores take at most kEaseScoreBytes on the device
 static void ease_score(cornac_hip_ease_t h, const int32_t *users, const int32_t *items, int64_t n, double *out) {
-    ease_check(h);
-    REQUIRE(n >= 0 && (n == 0 || (users && out)), "EASE: users / out are NULL");
-    for (int64_t b = 0; b < n; ++b) {
-        REQUIRE(users[b] >= 0 && users[b] < h->n_users, "EASE: user %d out of range", users[b]);
-        REQUIRE(!items || (items[b] >= 0 && items[b] < h->n_items), "EASE: item %d out of range", items ? items[b] : 0);
-    }
+    check_handle(h, "EASE handle");
+    check_ids("EASE", users, items, n, out, h->n_users, h->n_items);
     if (n == 0) return;
     const int64_t ni = h->n_items, per_user = items ? 1 : ni;
-    const int64_t cap = items ? (1 << 20) : std::min<int64_t>(65535, std::max<int64_t>(1, (256ll << 20) / ((int64_t)sizeof(double) * ni)));
+    const int64_t cap = items ? kEaseMaxPairs
+                              : std::min<int64_t>(kEaseMaxUsers, std::max<int64_t>(1, kEaseScoreBytes / ((int64_t)sizeof(double) * ni)));
     const int64_t B = std::min(n, cap);
-    if (h->out.n < (size_t)(B * per_user)) ease_alloc(h->out, (size_t)(B * per_user), "the scores");
-    if (h->users.n < (size_t)B) ease_alloc(h->users, (size_t)B, "the user ids");
-    if (items && h->items.n < (size_t)B) ease_alloc(h->items, (size_t)B, "the item ids");
-    for (int64_t b0 = 0; b0 < n; b0 += B) {
-        const int64_t nb = std::min(B, n - b0);
-        h->users.upload(users + b0, (size_t)nb, h->stream);
+    if (h->out.n < (size_t)(B * per_user)) alloc_named(h->out, (size_t)(B * per_user), "EASE", "the scores");
+    for_each_chunk("EASE", *h, users, items, n, B, [&](int64_t b0, int64_t nb) {
         if (items) {
-            h->items.upload(items + b0, (size_t)nb, h->stream);
             ease_score_pairs_kernel<<<dim3((unsigned)((nb + 255) / 256)), 256, 0, h->stream>>>(
-                h->row_ptr.p, h->row_idx.p, h->row_val.p, h->users.p, h->items.p, h->table.p, ni, nb, h->out.p);
+                h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->user_ids.p, h->item_ids.p, h->table.p, ni, nb, h->out.p);
         } else {
             ease_score_users_kernel<<<dim3((unsigned)((ni + kEaseBlock - 1) / kEaseBlock), (unsigned)nb), kEaseBlock, 0, h->stream>>>(
-                h->row_ptr.p, h->row_idx.p, h->row_val.p, h->users.p, h->table.p, ni, h->out.p);
+                h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->user_ids.p, h->table.p, ni, h->out.p);
         }
-        HIP_CHECK(hipGetLastError());
         h->out.download(out + b0 * per_user, (size_t)(nb * per_user), h->stream);
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-    }
+    });
 }
 
 int cornac_hip_ease_score_users(cornac_hip_ease_t h, const int32_t *users, int64_t n, double *out) {

@@ -16,9 +16,8 @@
 // reference's heap are stated without replaying it: every candidate above T; of the first k candidates (feed order) with
 // weight >= T, those at T, minus as many of their smallest ratings as there are candidates above T behind them.
 // The survivors are summed in one fixed order (lane-strided partial sums, then a butterfly).
-#include "common.h"
+#include "sparse_model.h"
 
-#include <algorithm>
 
 namespace chip {
 namespace {
@@ -28,35 +27,7 @@ constexpr int kKnnWave = 64;
 constexpr int kKnnMaxK = CORNAC_HIP_KNN_MAX_K;
 static_assert(kKnnMaxK <= kKnnWave, "the tie stage keeps one weight-T member of P per lane");
 
-template <class T>
-void knn_alloc(DevBuf<T> &b, size_t count, const char *what) {
-    b.release();
-    if (!count) return;
-    T *p = nullptr;
-    const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        fail(CORNAC_HIP_ERR_HIP, "KNN: cannot allocate %zu bytes of device memory for %s (%s)", count * sizeof(T), what,
-             hipGetErrorString(e));
-    }
-    b.p = p;
-    b.n = count;
-}
-
-void knn_check_csr(const char *name, int64_t n_rows, int64_t n_cols, const int64_t *indptr, const int32_t *indices,
-                   const double *data) {
-    REQUIRE(indptr != nullptr, "KNN: %s indptr is NULL", name);
-    REQUIRE(indptr[0] == 0, "KNN: %s indptr does not start at 0", name);
-    for (int64_t r = 0; r < n_rows; ++r) REQUIRE(indptr[r] <= indptr[r + 1], "KNN: %s indptr is not monotone", name);
-    const int64_t nnz = indptr[n_rows];
-    REQUIRE(nnz == 0 || (indices && data), "KNN: %s indices / data are NULL", name);
-    for (int64_t r = 0; r < n_rows; ++r)
-        for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-            REQUIRE(indices[e] >= 0 && indices[e] < n_cols, "KNN: %s column index out of range in row %lld", name, (long long)r);
-            REQUIRE(e == indptr[r] || indices[e - 1] < indices[e], "KNN: %s needs sorted indices without repeats (row %lld)",
-                    name, (long long)r);
-        }
-}
+constexpr int64_t kKnnDenseBytes = 64ll << 20;   // a scoring chunk's dense rows of Q
 
 // ---- similarity ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kKnnBlock) void knn_sim_rows_kernel(
@@ -337,22 +308,15 @@ struct KnnChunk {
     DevBuf<double> val;
 };
 
-struct cornac_hip_knn_sim {
-    int device = 0;
+struct cornac_hip_knn_sim : ModelHandle {
     int64_t n_rows = 0, n_cols = 0, nnz_in = 0;
-    hipStream_t stream = nullptr;
-    DevBuf<int64_t> row_ptr, col_ptr, indptr, offs;
-    DevBuf<int32_t> row_idx, col_idx;
-    DevBuf<double> row_val, col_val, S, D1, D2;
+    DevCsr rows, cols;   // W and its transpose
+    DevBuf<int64_t> indptr, offs;
+    DevBuf<double> S, D1, D2;
     DevBuf<int> counts;
     std::vector<std::unique_ptr<KnnChunk>> chunks;
     int64_t nnz_out = -1;   // -1: not run yet
 };
-
-static void knn_sim_check(cornac_hip_knn_sim_t h) {
-    REQUIRE(h != nullptr, "KNN similarity handle is NULL");
-    HIP_CHECK(hipSetDevice(h->device));
-}
 
 int cornac_hip_knn_sim_create(cornac_hip_knn_sim_t *out, int device, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
                               const int32_t *indices, const double *data) {
@@ -361,58 +325,25 @@ int cornac_hip_knn_sim_create(cornac_hip_knn_sim_t *out, int device, int64_t n_r
         *out = nullptr;
         REQUIRE(n_rows > 0 && n_cols > 0, "KNN: sizes must be positive");
         REQUIRE(n_rows < (1ll << 31) && n_cols < (1ll << 31), "KNN: row and column counts must fit int32");
-        knn_check_csr("W", n_rows, n_cols, indptr, indices, data);
-        const int64_t nnz = indptr[n_rows];
-        // the columns' entries, rows ascending (what data_mat.T.tocsr() holds, similarity.pyx:55): a counting sort
-        std::vector<int64_t> cptr((size_t)n_cols + 1, 0);
-        for (int64_t e = 0; e < nnz; ++e) ++cptr[(size_t)indices[e] + 1];
-        for (int64_t c = 0; c < n_cols; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
-        std::vector<int32_t> cidx((size_t)nnz);
-        std::vector<double> cval((size_t)nnz);
-        {
-            std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
-            for (int64_t r = 0; r < n_rows; ++r)
-                for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                    const int64_t d = fill[(size_t)indices[e]]++;
-                    cidx[(size_t)d] = (int32_t)r;
-                    cval[(size_t)d] = data[e];
-                }
-        }
-        use_device(device);
+        check_csr("KNN", "W", n_rows, n_cols, indptr, indices, data, kCsrValues);
+        // the columns' entries, rows ascending (what data_mat.T.tocsr() holds, similarity.pyx:55)
+        const HostCsr t = transpose_csr(n_rows, n_cols, indptr, indices, data);
         std::unique_ptr<cornac_hip_knn_sim> h(new cornac_hip_knn_sim());
-        h->device = device; h->n_rows = n_rows; h->n_cols = n_cols; h->nnz_in = nnz;
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        knn_alloc(h->row_ptr, (size_t)n_rows + 1, "W's row pointers");
-        knn_alloc(h->col_ptr, (size_t)n_cols + 1, "W's column pointers");
-        knn_alloc(h->indptr, (size_t)n_rows + 1, "the result's row pointers");
-        knn_alloc(h->row_idx, (size_t)nnz, "W's indices");
-        knn_alloc(h->col_idx, (size_t)nnz, "W's transposed indices");
-        knn_alloc(h->row_val, (size_t)nnz, "W's values");
-        knn_alloc(h->col_val, (size_t)nnz, "W's transposed values");
-        h->row_ptr.upload(indptr, (size_t)n_rows + 1, h->stream);
-        h->col_ptr.upload(cptr.data(), (size_t)n_cols + 1, h->stream);
-        if (nnz) {
-            h->row_idx.upload(indices, (size_t)nnz, h->stream);
-            h->row_val.upload(data, (size_t)nnz, h->stream);
-            h->col_idx.upload(cidx.data(), (size_t)nnz, h->stream);
-            h->col_val.upload(cval.data(), (size_t)nnz, h->stream);
-        }
+        h->open(device);
+        h->n_rows = n_rows; h->n_cols = n_cols; h->nnz_in = indptr[n_rows];
+        h->rows.upload("KNN", "W", n_rows, indptr, indices, data, h->stream);
+        h->cols.upload("KNN", "W transposed", t, h->stream);
+        alloc_named(h->indptr, (size_t)n_rows + 1, "KNN", "the result's row pointers");
         HIP_CHECK(hipStreamSynchronize(h->stream));
         *out = h.release();
     });
 }
 
-int cornac_hip_knn_sim_destroy(cornac_hip_knn_sim_t h) {
-    if (!h) return CORNAC_HIP_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    delete h;
-    return CORNAC_HIP_OK;
-}
+int cornac_hip_knn_sim_destroy(cornac_hip_knn_sim_t h) { return destroy_handle(h); }
 
 int cornac_hip_knn_sim_run(cornac_hip_knn_sim_t h, int64_t rows_per_pass) {
     return guarded([&] {
-        knn_sim_check(h);
+        check_handle(h, "KNN similarity handle");
         REQUIRE(rows_per_pass >= 0, "KNN: rows_per_pass must be >= 0 (0: chosen from the free device memory)");
         const int64_t n = h->n_rows;
         int64_t R = rows_per_pass;
@@ -430,17 +361,17 @@ int cornac_hip_knn_sim_run(cornac_hip_knn_sim_t h, int64_t rows_per_pass) {
         R = std::min<int64_t>(std::min(R, n), 1 << 20);
         h->chunks.clear();
         h->nnz_out = -1;
-        knn_alloc(h->S, (size_t)R * n, "the similarity accumulators (lower rows_per_pass)");
-        knn_alloc(h->D1, (size_t)R * n, "the similarity accumulators (lower rows_per_pass)");
-        knn_alloc(h->D2, (size_t)R * n, "the similarity accumulators (lower rows_per_pass)");
-        knn_alloc(h->counts, (size_t)R, "the row counts");
-        knn_alloc(h->offs, (size_t)R + 1, "the row offsets");
+        alloc_named(h->S, (size_t)R * n, "KNN", "the similarity accumulators (lower rows_per_pass)");
+        alloc_named(h->D1, (size_t)R * n, "KNN", "the similarity accumulators (lower rows_per_pass)");
+        alloc_named(h->D2, (size_t)R * n, "KNN", "the similarity accumulators (lower rows_per_pass)");
+        alloc_named(h->counts, (size_t)R, "KNN", "the row counts");
+        alloc_named(h->offs, (size_t)R + 1, "KNN", "the row offsets");
         HIP_CHECK(hipMemsetAsync(h->indptr.p, 0, sizeof(int64_t), h->stream));
         int64_t total = 0;
         for (int64_t r0 = 0; r0 < n; r0 += R) {
             const int64_t rows = std::min(R, n - r0);
             knn_sim_rows_kernel<<<dim3((unsigned)rows), kKnnBlock, 0, h->stream>>>(
-                h->row_ptr.p, h->row_idx.p, h->row_val.p, h->col_ptr.p, h->col_idx.p, h->col_val.p, n, r0, h->S.p, h->D1.p,
+                h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->cols.ptr.p, h->cols.idx.p, h->cols.val.p, n, r0, h->S.p, h->D1.p,
                 h->D2.p, h->counts.p);
             knn_prefix_kernel<<<1, kKnnBlock, 0, h->stream>>>(h->counts.p, rows, total, h->offs.p, h->indptr.p + r0);
             HIP_CHECK(hipGetLastError());
@@ -453,8 +384,8 @@ int cornac_hip_knn_sim_run(cornac_hip_knn_sim_t h, int64_t rows_per_pass) {
             ch->first = total;
             ch->count = count;
             if (count) {
-                knn_alloc(ch->idx, (size_t)count, "the similarity table's indices");
-                knn_alloc(ch->val, (size_t)count, "the similarity table's values");
+                alloc_named(ch->idx, (size_t)count, "KNN", "the similarity table's indices");
+                alloc_named(ch->val, (size_t)count, "KNN", "the similarity table's values");
                 knn_compact_kernel<<<dim3((unsigned)rows), kKnnBlock, 0, h->stream>>>(h->S.p, n, h->offs.p, ch->idx.p, ch->val.p);
                 HIP_CHECK(hipGetLastError());
             }
@@ -469,7 +400,7 @@ int cornac_hip_knn_sim_run(cornac_hip_knn_sim_t h, int64_t rows_per_pass) {
 
 int cornac_hip_knn_sim_nnz(cornac_hip_knn_sim_t h, int64_t *nnz) {
     return guarded([&] {
-        knn_sim_check(h);
+        check_handle(h, "KNN similarity handle");
         REQUIRE(nnz != nullptr, "nnz pointer is NULL");
         REQUIRE(h->nnz_out >= 0, "KNN: the similarity has not been run");
         *nnz = h->nnz_out;
@@ -478,7 +409,7 @@ int cornac_hip_knn_sim_nnz(cornac_hip_knn_sim_t h, int64_t *nnz) {
 
 int cornac_hip_knn_sim_get(cornac_hip_knn_sim_t h, int64_t *indptr, int32_t *indices, double *data) {
     return guarded([&] {
-        knn_sim_check(h);
+        check_handle(h, "KNN similarity handle");
         REQUIRE(h->nnz_out >= 0, "KNN: the similarity has not been run");
         REQUIRE(indptr && (h->nnz_out == 0 || (indices && data)), "KNN: result pointers are NULL");
         h->indptr.download(indptr, (size_t)h->n_rows + 1, h->stream);
@@ -492,20 +423,13 @@ int cornac_hip_knn_sim_get(cornac_hip_knn_sim_t h, int64_t *indptr, int32_t *ind
 }
 
 // ---- scorer handle -------------------------------------------------------------------------------------------------------
-struct cornac_hip_knn_scorer {
-    int device = 0, user_mode = 0;
+struct cornac_hip_knn_scorer : ModelHandle {
+    int user_mode = 0;
     int64_t n_items = 0, n_nb = 0, n_users = 0, max_row = 0;
-    hipStream_t stream = nullptr;
-    DevBuf<int64_t> n_ptr, q_ptr;
-    DevBuf<int32_t> n_idx, q_idx, rows, items;
-    DevBuf<double> n_val, q_val, v, cand_w, cand_s, out;
+    DevCsr N, Q;
+    DevBuf<double> v, cand_w, cand_s, out;
     int blocks = 0;
 };
-
-static void knn_scorer_check(cornac_hip_knn_scorer_t h) {
-    REQUIRE(h != nullptr, "KNN scorer handle is NULL");
-    HIP_CHECK(hipSetDevice(h->device));
-}
 
 int cornac_hip_knn_scorer_create(cornac_hip_knn_scorer_t *out, int device, int64_t n_items, int64_t n_neighbours,
                                  int64_t n_users, const int64_t *n_indptr, const int32_t *n_indices, const double *n_data,
@@ -515,73 +439,47 @@ int cornac_hip_knn_scorer_create(cornac_hip_knn_scorer_t *out, int device, int64
         *out = nullptr;
         REQUIRE(n_items > 0 && n_neighbours > 0 && n_users > 0, "KNN: sizes must be positive");
         REQUIRE(n_items < (1ll << 31) && n_neighbours < (1ll << 31) && n_users < (1ll << 31), "KNN: sizes must fit int32");
-        knn_check_csr("N", n_items, n_neighbours, n_indptr, n_indices, n_data);
-        knn_check_csr("Q", n_users, n_neighbours, q_indptr, q_indices, q_data);
-        use_device(device);
+        check_csr("KNN", "N", n_items, n_neighbours, n_indptr, n_indices, n_data, kCsrValues);
+        check_csr("KNN", "Q", n_users, n_neighbours, q_indptr, q_indices, q_data, kCsrValues);
         std::unique_ptr<cornac_hip_knn_scorer> h(new cornac_hip_knn_scorer());
-        h->device = device; h->user_mode = user_mode != 0;
+        h->open(device);
+        h->user_mode = user_mode != 0;
         h->n_items = n_items; h->n_nb = n_neighbours; h->n_users = n_users;
         for (int64_t i = 0; i < n_items; ++i) h->max_row = std::max(h->max_row, n_indptr[i + 1] - n_indptr[i]);
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        const int64_t nn = n_indptr[n_items], qn = q_indptr[n_users];
-        knn_alloc(h->n_ptr, (size_t)n_items + 1, "N's row pointers");
-        knn_alloc(h->q_ptr, (size_t)n_users + 1, "Q's row pointers");
-        knn_alloc(h->n_idx, (size_t)nn, "N's indices");
-        knn_alloc(h->n_val, (size_t)nn, "N's values");
-        knn_alloc(h->q_idx, (size_t)qn, "Q's indices");
-        knn_alloc(h->q_val, (size_t)qn, "Q's values");
-        h->n_ptr.upload(n_indptr, (size_t)n_items + 1, h->stream);
-        h->q_ptr.upload(q_indptr, (size_t)n_users + 1, h->stream);
-        if (nn) { h->n_idx.upload(n_indices, (size_t)nn, h->stream); h->n_val.upload(n_data, (size_t)nn, h->stream); }
-        if (qn) { h->q_idx.upload(q_indices, (size_t)qn, h->stream); h->q_val.upload(q_data, (size_t)qn, h->stream); }
+        h->N.upload("KNN", "N", n_items, n_indptr, n_indices, n_data, h->stream);
+        h->Q.upload("KNN", "Q", n_users, q_indptr, q_indices, q_data, h->stream);
         // one candidate buffer of max_row (weight, rating) pairs per resident workgroup: at most 1 GiB of them
         const int64_t per_block = std::max<int64_t>(h->max_row, 1) * 2 * (int64_t)sizeof(double);
         h->blocks = (int)std::max<int64_t>(1, std::min<int64_t>(8192, (1ll << 30) / per_block));
-        knn_alloc(h->cand_w, (size_t)h->blocks * (size_t)std::max<int64_t>(h->max_row, 1), "the candidate buffers");
-        knn_alloc(h->cand_s, (size_t)h->blocks * (size_t)std::max<int64_t>(h->max_row, 1), "the candidate buffers");
+        alloc_named(h->cand_w, (size_t)h->blocks * (size_t)std::max<int64_t>(h->max_row, 1), "KNN", "the candidate buffers");
+        alloc_named(h->cand_s, (size_t)h->blocks * (size_t)std::max<int64_t>(h->max_row, 1), "KNN", "the candidate buffers");
         HIP_CHECK(hipStreamSynchronize(h->stream));
         *out = h.release();
     });
 }
 
-int cornac_hip_knn_scorer_destroy(cornac_hip_knn_scorer_t h) {
-    if (!h) return CORNAC_HIP_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    delete h;
-    return CORNAC_HIP_OK;
-}
+int cornac_hip_knn_scorer_destroy(cornac_hip_knn_scorer_t h) { return destroy_handle(h); }
 
-// users[0..n) (and items[0..n) for pairs) in chunks whose dense rows of Q take at most 64 MiB
+// users[0..n) (and items[0..n) for pairs) in chunks whose dense rows of Q take at most kKnnDenseBytes
 static void knn_score(cornac_hip_knn_scorer_t h, const int32_t *users, const int32_t *items, int64_t n, int k, double *out) {
-    knn_scorer_check(h);
-    REQUIRE(n >= 0 && (n == 0 || (users && out)), "KNN: users / out are NULL");
+    check_handle(h, "KNN scorer handle");
     REQUIRE(k >= 1 && k <= kKnnMaxK, "KNN: k = %d is outside 1 .. %d (CORNAC_HIP_KNN_MAX_K)", k, kKnnMaxK);
-    for (int64_t b = 0; b < n; ++b) {
-        REQUIRE(users[b] >= 0 && users[b] < h->n_users, "KNN: user %d out of range", users[b]);
-        REQUIRE(!items || (items[b] >= 0 && items[b] < h->n_items), "KNN: item %d out of range", items ? items[b] : 0);
-    }
+    check_ids("KNN", users, items, n, out, h->n_users, h->n_items);
     if (n == 0) return;
     const int64_t per_task_row = items ? 1 : h->n_items;
-    const int64_t B = std::max<int64_t>(1, std::min<int64_t>(n, (64ll << 20) / ((int64_t)sizeof(double) * h->n_nb)));
-    if (h->v.n < (size_t)(B * h->n_nb)) knn_alloc(h->v, (size_t)(B * h->n_nb), "the users' dense rows");
-    if (h->out.n < (size_t)(B * per_task_row)) knn_alloc(h->out, (size_t)(B * per_task_row), "the scores");
-    if (h->rows.n < (size_t)B) knn_alloc(h->rows, (size_t)B, "the user ids");
-    if (items && h->items.n < (size_t)B) knn_alloc(h->items, (size_t)B, "the item ids");
-    for (int64_t b0 = 0; b0 < n; b0 += B) {
-        const int64_t nb = std::min(B, n - b0), tasks = nb * per_task_row;
-        h->rows.upload(users + b0, (size_t)nb, h->stream);
-        if (items) h->items.upload(items + b0, (size_t)nb, h->stream);
-        knn_dense_rows_kernel<<<dim3((unsigned)nb), kKnnBlock, 0, h->stream>>>(h->q_ptr.p, h->q_idx.p, h->q_val.p, h->rows.p,
+    const int64_t B = std::max<int64_t>(1, std::min<int64_t>(n, kKnnDenseBytes / ((int64_t)sizeof(double) * h->n_nb)));
+    if (h->v.n < (size_t)(B * h->n_nb)) alloc_named(h->v, (size_t)(B * h->n_nb), "KNN", "the users' dense rows");
+    if (h->out.n < (size_t)(B * per_task_row)) alloc_named(h->out, (size_t)(B * per_task_row), "KNN", "the scores");
+    for_each_chunk("KNN", *h, users, items, n, B, [&](int64_t b0, int64_t nb) {
+        const int64_t tasks = nb * per_task_row;
+        knn_dense_rows_kernel<<<dim3((unsigned)nb), kKnnBlock, 0, h->stream>>>(h->Q.ptr.p, h->Q.idx.p, h->Q.val.p, h->user_ids.p,
                                                                               h->n_nb, h->v.p);
         const unsigned grid = (unsigned)std::min<int64_t>(tasks, h->blocks);
-        knn_score_kernel<<<dim3(grid), kKnnWave, 0, h->stream>>>(h->n_ptr.p, h->n_idx.p, h->n_val.p, h->v.p, h->n_nb, h->n_items,
-                                                                 items ? h->items.p : nullptr, tasks, k, h->user_mode, h->max_row,
+        knn_score_kernel<<<dim3(grid), kKnnWave, 0, h->stream>>>(h->N.ptr.p, h->N.idx.p, h->N.val.p, h->v.p, h->n_nb, h->n_items,
+                                                                 items ? h->item_ids.p : nullptr, tasks, k, h->user_mode, h->max_row,
                                                                  h->cand_w.p, h->cand_s.p, h->out.p);
-        HIP_CHECK(hipGetLastError());
         h->out.download(out + b0 * per_task_row, (size_t)tasks, h->stream);
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-    }
+    });
 }
 
 int cornac_hip_knn_scorer_score_users(cornac_hip_knn_scorer_t h, const int32_t *users, int64_t n, int k, double *out) {

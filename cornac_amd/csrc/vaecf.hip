@@ -21,11 +21,8 @@
 //
 // The three B x h x I products are register-tiled vector FMA (64 x 64 tiles, 4 x 4 per thread, operands staged through
 // LDS): f32-input MFMA has vector FMA's peak on this part, and the chains keep a fixed ascending order this way.
-#include "common.h"
+#include "sparse_model.h"
 #include "rng.h"
-
-#include <algorithm>
-#include <cmath>
 
 namespace chip {
 namespace {
@@ -34,6 +31,7 @@ constexpr int kVaeBlock = 256;
 constexpr int kVaeMaxK = 256, kVaeMaxH = 1024, kVaeMaxBatch = 1024;
 constexpr int kVaeTile = 64, kVaeTk = 16;
 constexpr float kVaeEps = 1e-10f;
+constexpr int64_t kVaeScoreBytes = 256ll << 20;   // a scoring chunk's logits (at most kVaeMaxBatch users)
 enum { ACT_TANH = 0, ACT_SIGMOID, ACT_RELU, ACT_RELU6, ACT_ELU, ACT_COUNT };
 enum { LIK_MULT = 0, LIK_BERN, LIK_GAUS, LIK_POIS, LIK_COUNT };
 
@@ -400,15 +398,12 @@ __global__ void vae_gather_pairs_kernel(const float *__restrict__ p, int64_t I, 
 
 using namespace chip;
 
-struct cornac_hip_vaecf {
-    int device = 0;
+struct cornac_hip_vaecf : ModelHandle {
     int64_t n_users = 0, n_items = 0, nnz = 0;
     int k = 0, h = 0, act = 0, lik = 0;
     int64_t t = 0;   // Adam's step counter
     VaeLayout L{};
-    hipStream_t stream = nullptr;
-    DevBuf<int64_t> row_ptr, col_ptr;
-    DevBuf<int32_t> row_idx, col_idx, users, items;
+    DevCsr rows, cols;   // the binarised X and its transpose: no values
     DevBuf<float> w, m, v, eps, loss;
     // per call, sized for `cap` rows
     int64_t cap = 0;
@@ -416,11 +411,6 @@ struct cornac_hip_vaecf {
     int64_t kchunk = 0;
     DevBuf<float> h1, d1, mu, sd, z, h2, d2, kl, logits, part, ga2, gmu, glv, ga1, out;
 };
-
-static void vae_check(cornac_hip_vaecf_t h) {
-    REQUIRE(h != nullptr, "VAECF handle is NULL");
-    HIP_CHECK(hipSetDevice(h->device));
-}
 
 static void vae_table_dims(cornac_hip_vaecf_t h, int64_t off[10], int64_t rows[10], int64_t cols[10]) {
     const int64_t I = h->n_items, hh = h->h, k = h->k;
@@ -434,11 +424,12 @@ static void vae_ensure(cornac_hip_vaecf_t h, int64_t cap) {
     const size_t I = (size_t)h->n_items, hh = (size_t)h->h, k = (size_t)h->k, c = (size_t)cap;
     h->n_split = (int)std::min<int64_t>(32, std::max<int64_t>(1, (h->n_items + 4095) / 4096));
     h->kchunk = ((h->n_items + h->n_split - 1) / h->n_split + kVaeTk - 1) / kVaeTk * kVaeTk;
-    for (DevBuf<float> *b : {&h->h1, &h->d1, &h->h2, &h->d2, &h->ga2, &h->ga1}) b->alloc(c * hh);
-    for (DevBuf<float> *b : {&h->mu, &h->sd, &h->z, &h->gmu, &h->glv}) b->alloc(c * k);
-    h->kl.alloc(c);
-    h->logits.alloc(c * I);
-    h->part.alloc((size_t)h->n_split * c * hh);
+    const char *what = "a batch's activations and logits";
+    for (DevBuf<float> *b : {&h->h1, &h->d1, &h->h2, &h->d2, &h->ga2, &h->ga1}) alloc_named(*b, c * hh, "VAECF", what);
+    for (DevBuf<float> *b : {&h->mu, &h->sd, &h->z, &h->gmu, &h->glv}) alloc_named(*b, c * k, "VAECF", what);
+    alloc_named(h->kl, c, "VAECF", what);
+    alloc_named(h->logits, c * I, "VAECF", what);
+    alloc_named(h->part, (size_t)h->n_split * c * hh, "VAECF", what);
     h->cap = cap;
 }
 
@@ -453,30 +444,11 @@ int cornac_hip_vaecf_create(cornac_hip_vaecf_t *out, int device, int64_t n_users
         REQUIRE(hidden >= 1 && hidden <= kVaeMaxH, "VAECF: h = %d is outside the supported range 1 <= h <= %d", hidden, kVaeMaxH);
         REQUIRE(act >= 0 && act < ACT_COUNT, "VAECF: unknown activation %d", act);
         REQUIRE(likelihood >= 0 && likelihood < LIK_COUNT, "VAECF: unknown likelihood %d", likelihood);
-        REQUIRE(indptr != nullptr, "VAECF: indptr is NULL");
-        REQUIRE(indptr[0] == 0, "VAECF: indptr does not start at 0");
-        for (int64_t u = 0; u < n_users; ++u) REQUIRE(indptr[u] <= indptr[u + 1], "VAECF: indptr is not monotone");
-        const int64_t nnz = indptr[n_users];
-        REQUIRE(nnz == 0 || indices, "VAECF: indices are NULL");
-        for (int64_t u = 0; u < n_users; ++u)
-            for (int64_t e = indptr[u]; e < indptr[u + 1]; ++e) {
-                REQUIRE(indices[e] >= 0 && indices[e] < n_items, "VAECF: item index out of range in row %lld", (long long)u);
-                REQUIRE(e == indptr[u] || indices[e - 1] < indices[e], "VAECF: X needs sorted indices without repeats (row %lld)",
-                        (long long)u);
-            }
-        // the items' users, ascending: a counting sort
-        std::vector<int64_t> cptr((size_t)n_items + 1, 0);
-        for (int64_t e = 0; e < nnz; ++e) ++cptr[(size_t)indices[e] + 1];
-        for (int64_t c = 0; c < n_items; ++c) cptr[(size_t)c + 1] += cptr[(size_t)c];
-        std::vector<int32_t> cidx((size_t)nnz);
-        {
-            std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
-            for (int64_t u = 0; u < n_users; ++u)
-                for (int64_t e = indptr[u]; e < indptr[u + 1]; ++e) cidx[(size_t)fill[(size_t)indices[e]]++] = (int32_t)u;
-        }
-        use_device(device);
+        check_csr("VAECF", "X", n_users, n_items, indptr, indices, nullptr, kCsrNoValues);
+        const HostCsr t = transpose_csr(n_users, n_items, indptr, indices, nullptr);   // the items' users, ascending
         std::unique_ptr<cornac_hip_vaecf> h(new cornac_hip_vaecf());
-        h->device = device; h->n_users = n_users; h->n_items = n_items; h->nnz = nnz;
+        h->open(device);
+        h->n_users = n_users; h->n_items = n_items; h->nnz = indptr[n_users];
         h->k = k; h->h = hidden; h->act = act; h->lik = likelihood;
         {
             const int64_t I = n_items, hh = hidden, kk = k;
@@ -484,35 +456,20 @@ int cornac_hip_vaecf_create(cornac_hip_vaecf_t *out, int device, int64_t n_users
             L.W1 = 0; L.b1 = L.W1 + I * hh; L.Wm = L.b1 + hh; L.bm = L.Wm + kk * hh; L.Wv = L.bm + kk; L.bv = L.Wv + kk * hh;
             L.D0 = L.bv + kk; L.c0 = L.D0 + hh * kk; L.D1 = L.c0 + hh; L.c1 = L.D1 + I * hh; L.total = L.c1 + I;
         }
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         for (DevBuf<float> *b : {&h->w, &h->m, &h->v}) {
-            b->alloc((size_t)h->L.total);
+            alloc_named(*b, (size_t)h->L.total, "VAECF", "the tables and Adam's moments");
             HIP_CHECK(hipMemsetAsync(b->p, 0, b->n * sizeof(float), h->stream));
         }
-        h->eps.alloc((size_t)n_users * (size_t)k);
-        h->loss.alloc((size_t)n_users);
-        h->row_ptr.alloc((size_t)n_users + 1);
-        h->col_ptr.alloc((size_t)n_items + 1);
-        h->row_idx.alloc((size_t)std::max<int64_t>(nnz, 1));
-        h->col_idx.alloc((size_t)std::max<int64_t>(nnz, 1));
-        h->row_ptr.upload(indptr, (size_t)n_users + 1, h->stream);
-        h->col_ptr.upload(cptr.data(), (size_t)n_items + 1, h->stream);
-        if (nnz) {
-            h->row_idx.upload(indices, (size_t)nnz, h->stream);
-            h->col_idx.upload(cidx.data(), (size_t)nnz, h->stream);
-        }
+        alloc_named(h->eps, (size_t)n_users * (size_t)k, "VAECF", "the noise");
+        alloc_named(h->loss, (size_t)n_users, "VAECF", "the users' losses");
+        h->rows.upload("VAECF", "X", n_users, indptr, indices, nullptr, h->stream);
+        h->cols.upload("VAECF", "X transposed", t, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         *out = h.release();
     });
 }
 
-int cornac_hip_vaecf_destroy(cornac_hip_vaecf_t h) {
-    if (!h) return CORNAC_HIP_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    delete h;
-    return CORNAC_HIP_OK;
-}
+int cornac_hip_vaecf_destroy(cornac_hip_vaecf_t h) { return destroy_handle(h); }
 
 // host <-> device copies of the ten tables of one buffer, in the reference's shapes (W1 is [h x I] there, [I x h] here)
 static void vae_put(cornac_hip_vaecf_t h, DevBuf<float> &buf, const float *const *tables) {
@@ -554,7 +511,7 @@ static void vae_get(cornac_hip_vaecf_t h, const DevBuf<float> &buf, float *const
 
 int cornac_hip_vaecf_set_params(cornac_hip_vaecf_t h, const float *const *tables) {
     return guarded([&] {
-        vae_check(h);
+        check_handle(h, "VAECF handle");
         REQUIRE(tables != nullptr, "VAECF: tables is NULL");
         vae_put(h, h->w, tables);
     });
@@ -562,7 +519,7 @@ int cornac_hip_vaecf_set_params(cornac_hip_vaecf_t h, const float *const *tables
 
 int cornac_hip_vaecf_get_params(cornac_hip_vaecf_t h, float *const *tables) {
     return guarded([&] {
-        vae_check(h);
+        check_handle(h, "VAECF handle");
         REQUIRE(tables != nullptr, "VAECF: tables is NULL");
         vae_get(h, h->w, tables);
     });
@@ -570,7 +527,7 @@ int cornac_hip_vaecf_get_params(cornac_hip_vaecf_t h, float *const *tables) {
 
 int cornac_hip_vaecf_get_state(cornac_hip_vaecf_t h, float *const *m, float *const *v, int64_t *t) {
     return guarded([&] {
-        vae_check(h);
+        check_handle(h, "VAECF handle");
         if (m) vae_get(h, h->m, m);
         if (v) vae_get(h, h->v, v);
         if (t) *t = h->t;
@@ -579,7 +536,7 @@ int cornac_hip_vaecf_get_state(cornac_hip_vaecf_t h, float *const *m, float *con
 
 int cornac_hip_vaecf_reset_optimizer(cornac_hip_vaecf_t h) {
     return guarded([&] {
-        vae_check(h);
+        check_handle(h, "VAECF handle");
         HIP_CHECK(hipMemsetAsync(h->m.p, 0, h->m.n * sizeof(float), h->stream));
         HIP_CHECK(hipMemsetAsync(h->v.p, 0, h->v.n * sizeof(float), h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -605,7 +562,7 @@ static void vae_logits(cornac_hip_vaecf_t h, int64_t nb) {
 int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float lr, float beta, const float *eps, uint64_t seed,
                                double *loss_sum, double *step_loss) {
     return guarded([&] {
-        vae_check(h);
+        check_handle(h, "VAECF handle");
         REQUIRE(batch_size >= 1 && batch_size <= kVaeMaxBatch, "VAECF: batch_size = %lld is outside the supported range 1 <= batch_size <= %d",
                 (long long)batch_size, kVaeMaxBatch);
         REQUIRE(std::isfinite(lr) && std::isfinite(beta), "VAECF: lr and beta must be finite");
@@ -623,11 +580,11 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
             h->t += 1;
             const double bc1 = 1.0 - std::pow(0.9, (double)h->t), bc2 = 1.0 - std::pow(0.999, (double)h->t);
             const VaeAdam ad{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
-            vae_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->row_ptr.p, h->row_idx.p, nullptr, u0, w, L, (int)hh, (int)k, h->act,
+            vae_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, nullptr, u0, w, L, (int)hh, (int)k, h->act,
                                                                         h->eps.p, h->h1.p, h->d1.p, h->mu.p, h->sd.p, h->z.p, h->h2.p,
                                                                         h->d2.p, h->kl.p);
             vae_logits(h, nb);
-            vae_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->row_ptr.p, h->row_idx.p, nullptr, u0, h->logits.p, I, h->lik, 1,
+            vae_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, nullptr, u0, h->logits.p, I, h->lik, 1,
                                                                             inv_b, beta, h->kl.p, h->loss.p);
             // gh2 partials: go[nb x I] D1[I x h] over n_split item ranges
             vae_gemm_kernel<true, false, 1><<<dim3(vae_tiles(nb, hh), 1, (unsigned)h->n_split), kVaeBlock, 0, h->stream>>>(
@@ -637,7 +594,7 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
                                                                         h->glv.p, h->ga1.p);
             vae_small_adam_kernel<<<vae_grid(small), kVaeBlock, 0, h->stream>>>(w, am, av, L, (int)hh, (int)k, nb, h->ga2.p, h->z.p, h->gmu.p,
                                                                                h->glv.p, h->h1.p, h->ga1.p, ad);
-            vae_w1_adam_kernel<<<vae_grid(I * hh), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, (int)hh, u0, nb, h->col_ptr.p, h->col_idx.p,
+            vae_w1_adam_kernel<<<vae_grid(I * hh), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, (int)hh, u0, nb, h->cols.ptr.p, h->cols.idx.p,
                                                                              h->ga1.p, ad);
             vae_c1_adam_kernel<<<vae_grid(I), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, nb, h->logits.p, ad);
             // D1: (go^T h2)[I x h], each tile applied at once
@@ -663,41 +620,31 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
 
 // users[0 .. n) in chunks: encode at z = mu; then h2 to the host (what == 0), p rows (1) or p[q, items[q]] (2)
 static void vae_predict(cornac_hip_vaecf_t h, const int32_t *users, const int32_t *items, int64_t n, float *out, int what) {
-    vae_check(h);
-    REQUIRE(n >= 0 && (n == 0 || (users && out)), "VAECF: users / out are NULL");
-    for (int64_t b = 0; b < n; ++b) {
-        REQUIRE(users[b] >= 0 && users[b] < h->n_users, "VAECF: user %d out of range", users[b]);
-        REQUIRE(!items || (items[b] >= 0 && items[b] < h->n_items), "VAECF: item %d out of range", items ? items[b] : 0);
-    }
+    check_handle(h, "VAECF handle");
+    check_ids("VAECF", users, items, n, out, h->n_users, h->n_items);
     if (n == 0) return;
     const int64_t I = h->n_items, hh = h->h;
-    const int64_t B = std::min<int64_t>(n, std::max<int64_t>(1, std::min<int64_t>(kVaeMaxBatch, (256ll << 20) / (4 * I))));
+    const int64_t B = std::min<int64_t>(n, std::max<int64_t>(1, std::min<int64_t>(kVaeMaxBatch, kVaeScoreBytes / (4 * I))));
     vae_ensure(h, B);
-    h->users.ensure((size_t)B);
-    if (items) { h->items.ensure((size_t)B); h->out.ensure((size_t)B); }
-    for (int64_t b0 = 0; b0 < n; b0 += B) {
-        const int64_t nb = std::min(B, n - b0);
-        h->users.upload(users + b0, (size_t)nb, h->stream);
-        vae_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->row_ptr.p, h->row_idx.p, h->users.p, 0, h->w.p, h->L, (int)hh, h->k, h->act,
-                                                                    nullptr, h->h1.p, h->d1.p, h->mu.p, h->sd.p, h->z.p, h->h2.p, h->d2.p,
-                                                                    h->kl.p);
+    if (items && h->out.n < (size_t)B) alloc_named(h->out, (size_t)B, "VAECF", "the scores");
+    for_each_chunk("VAECF", *h, users, items, n, B, [&](int64_t b0, int64_t nb) {
+        vae_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->user_ids.p, 0, h->w.p, h->L, (int)hh, h->k,
+                                                                    h->act, nullptr, h->h1.p, h->d1.p, h->mu.p, h->sd.p, h->z.p, h->h2.p,
+                                                                    h->d2.p, h->kl.p);
         if (what == 0) {
             h->h2.download(out + b0 * hh, (size_t)(nb * hh), h->stream);
-        } else {
-            vae_logits(h, nb);
-            vae_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->row_ptr.p, h->row_idx.p, h->users.p, 0, h->logits.p, I, h->lik, 0,
-                                                                            0.f, 0.f, h->kl.p, h->loss.p);
-            if (what == 1) {
-                h->logits.download(out + b0 * I, (size_t)(nb * I), h->stream);
-            } else {
-                h->items.upload(items + b0, (size_t)nb, h->stream);
-                vae_gather_pairs_kernel<<<vae_grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->items.p, nb, h->out.p);
-                h->out.download(out + b0, (size_t)nb, h->stream);
-            }
+            return;
         }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-    }
+        vae_logits(h, nb);
+        vae_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->user_ids.p, 0, h->logits.p, I, h->lik, 0,
+                                                                        0.f, 0.f, h->kl.p, h->loss.p);
+        if (what == 1) {
+            h->logits.download(out + b0 * I, (size_t)(nb * I), h->stream);
+        } else {
+            vae_gather_pairs_kernel<<<vae_grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->item_ids.p, nb, h->out.p);
+            h->out.download(out + b0, (size_t)nb, h->stream);
+        }
+    });
 }
 
 int cornac_hip_vaecf_encode_users(cornac_hip_vaecf_t h, const int32_t *users, int64_t n, float *h2_out) {

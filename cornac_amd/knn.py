@@ -13,7 +13,7 @@ from scipy.sparse import coo_matrix
 
 from . import _lib
 from .pmf import _get_rng
-from .recommender import Recommender, ScoreException, _table_fingerprint, clip
+from .recommender import HandleScoredRecommender, Recommender, ScoreException, _table_fingerprint
 
 EPS = 1e-8
 SIMILARITIES = ["cosine", "pearson"]
@@ -61,7 +61,7 @@ def _bm25_weight(ui_mat):
     return (K1 + 1.0) / (K1 * length_norm[X.row] + X.data) * idf[X.col] + EPS
 
 
-class _KNN(Recommender):
+class _KNN(HandleScoredRecommender):
     """What the two models share: the reference's constructor (plus `device`), the preparation of the weight matrix, the
     device scorer's life cycle and the prediction surface."""
 
@@ -117,67 +117,27 @@ class _KNN(Recommender):
         self._drop_scorer()
         return self
 
-    # ---- prediction -------------------------------------------------------------------------------
+    # ---- prediction (recom_knn.py:212-264 / :389-435: the user's mean plus the weighted average over the k nearest neighbours)
     def _tables(self):
         """(N, Q) of the device scorer"""
         raise NotImplementedError
 
-    def _scorer_row_count(self):
-        # no factor tables: rank() and the evaluators take the per-user flow over score(), as PMF's and HPF's do
-        return 0
+    def _handle_key(self):
+        return tuple((id(m),) + tuple(_table_fingerprint(a) for a in (m.indptr, m.indices, m.data)) for m in self._tables())
 
-    @property
-    def batch_num_items(self):
-        return self.num_items
-
-    def register_exclusions(self, token, user_indices, ex_ptr, ex_idx):
-        return False   # no factor-table scorer to keep the lists on: the evaluators' per-user flow needs none
-
-    def _knn_scorer(self):
-        N, Q = self._tables()
-        key = tuple((id(m),) + tuple(_table_fingerprint(a) for a in (m.indptr, m.indices, m.data)) for m in (N, Q))
-        if self.__dict__.get("_scorer") is None or self.__dict__.get("_scorer_key") != key:
-            self._drop_scorer()
-            self._scorer = _lib.KnnScorer(N, Q, self._USER_MODE, device=self.device)
-            self._scorer_key = key
-        return self._scorer
+    def _build_handle(self):
+        return _lib.KnnScorer(*self._tables(), self._USER_MODE, device=self.device)
 
     def _check_k(self):
         if not 1 <= int(self.k) <= KNN_MAX_K:
             raise ValueError("Invalid k = {}: the device scores with 1 <= k <= {} neighbours".format(self.k, KNN_MAX_K))
         return int(self.k)
 
-    def _unknown(self, user_idx, item_idx):
-        raise NotImplementedError
+    def _user_rows(self, handle, users):
+        return self.mean_arr[np.asarray(users)][:, None] + handle.score_users(users, self._check_k())
 
-    def score(self, user_idx, item_idx=None):
-        """recom_knn.py:212-264 / :389-435: the user's mean plus the weighted average over the k nearest neighbours"""
-        self._unknown(user_idx, item_idx)
-        sc, k = self._knn_scorer(), self._check_k()
-        if item_idx is not None:
-            return self.mean_arr[user_idx] + sc.score_pairs([user_idx], [item_idx], k)[0]
-        return self.mean_arr[user_idx] + sc.score_users([user_idx], k)[0]
-
-    def score_batch(self, user_indices):
-        """`score(u)` for every listed user in one call: [n, num_items] float64"""
-        users = np.asarray(user_indices, dtype=np.int64).ravel()
-        for u in users:
-            self._unknown(int(u), None)
-        return self.mean_arr[users][:, None] + self._knn_scorer().score_users(users, self._check_k())
-
-    def rate_batch(self, user_indices, item_indices, clipping=True):
-        """`rate()` for many pairs (the rating metrics' loop, cornac/eval_methods/base_method.py:35-105) in one call; pairs
-        with an unknown user or item go through `rate()` itself"""
-        u = np.asarray(user_indices, dtype=np.int64)
-        i = np.asarray(item_indices, dtype=np.int64)
-        known = (u >= 0) & (u < self.num_users) & (i >= 0) & (i < self.num_items)
-        out = np.empty(len(u), dtype=np.float64)
-        if known.any():
-            pred = self.mean_arr[u[known]] + self._knn_scorer().score_pairs(u[known], i[known], self._check_k())
-            out[known] = clip(pred, self.min_rating, self.max_rating) if clipping else pred
-        for p in np.flatnonzero(~known):
-            out[p] = self.rate(int(u[p]), int(i[p]), clipping)
-        return out
+    def _pair_values(self, handle, users, items):
+        return self.mean_arr[np.asarray(users)] + handle.score_pairs(users, items, self._check_k())
 
 
 class UserKNN(_KNN):
@@ -233,9 +193,3 @@ class ItemKNN(_KNN):
 
     def _tables(self):
         return self.sim_mat, self.ui_mat
-
-    def _unknown(self, user_idx, item_idx):
-        if self.is_unknown_user(user_idx):
-            raise ScoreException("Can't make score prediction for user %d" % user_idx)
-        if item_idx is not None and self.is_unknown_item(item_idx):
-            raise ScoreException("Can't make score prediction for item %d" % item_idx)

@@ -451,4 +451,92 @@ class Recommender(_RecommenderRoot):
         return [names[i] for i in ranked]
 
 
+class HandleScoredRecommender(Recommender):
+    """A model whose scores come from a device handle of its own (the KNN tables, EASE's item-item table, VAECF's network)
+    rather than from factor tables.  A subclass supplies `_handle_key()` (fingerprints of the host arrays the handle
+    holds) and `_build_handle()`, and, where its scores are not the handle's as they come, the two hooks `_user_rows` and
+    `_pair_values`.  The handle is cached in the attribute pair `_HANDLE_ATTRS` and rebuilt when the key changes; `rank()` and
+    the evaluators take the per-user flow over score(), as PMF's and HPF's do."""
+    _HANDLE_ATTRS = ("_scorer", "_scorer_key")
+
+    def _handle_key(self):
+        raise NotImplementedError
+
+    def _build_handle(self):
+        """a new handle holding what `_handle_key()` describes (closed again if filling it fails)"""
+        raise NotImplementedError
+
+    def _user_rows(self, handle, users):
+        """scores [n, num_items] of the listed (known) users"""
+        return handle.score_users(users)
+
+    def _pair_values(self, handle, users, items):
+        """scores [n] of the listed (known) pairs"""
+        return handle.score_pairs(users, items)
+
+    def _keep_handle(self, handle):
+        """`handle` holds the model's arrays as they are now (`fit` hands over the one it trained with)"""
+        setattr(self, self._HANDLE_ATTRS[0], handle)
+        setattr(self, self._HANDLE_ATTRS[1], self._handle_key())
+
+    def _handle(self):
+        """the cached handle, or a new one after load() / an edit of the arrays it holds"""
+        attr, key_attr = self._HANDLE_ATTRS
+        if self.__dict__.get(attr) is None or self.__dict__.get(key_attr) != self._handle_key():
+            self._drop_scorer()
+            self._keep_handle(self._build_handle())
+        return self.__dict__[attr]
+
+    def _drop_scorer(self):
+        Recommender._drop_scorer(self)
+        handle = self.__dict__.pop(self._HANDLE_ATTRS[0], None)
+        self.__dict__.pop(self._HANDLE_ATTRS[1], None)
+        if handle is not None:
+            handle.close()
+
+    def _scorer_row_count(self):
+        return 0   # no factor tables
+
+    @property
+    def batch_num_items(self):
+        return self.num_items
+
+    def register_exclusions(self, token, user_indices, ex_ptr, ex_idx):
+        return False   # no factor-table scorer to keep the lists on: the evaluators' per-user flow needs none
+
+    def _unknown(self, user_idx, item_idx):
+        if self.is_unknown_user(user_idx):
+            raise ScoreException("Can't make score prediction for user %d" % user_idx)
+        if item_idx is not None and self.is_unknown_item(item_idx):
+            raise ScoreException("Can't make score prediction for item %d" % item_idx)
+
+    def score(self, user_idx, item_idx=None):
+        self._unknown(user_idx, item_idx)
+        handle = self._handle()
+        if item_idx is not None:
+            return self._pair_values(handle, [user_idx], [item_idx])[0]
+        return self._user_rows(handle, [user_idx])[0]
+
+    def score_batch(self, user_indices):
+        """`score(u)` for every listed user in one call: [n, num_items]"""
+        users = np.asarray(user_indices, dtype=np.int64).ravel()
+        for u in users:
+            self._unknown(int(u), None)
+        return self._user_rows(self._handle(), users)
+
+    def rate_batch(self, user_indices, item_indices, clipping=True):
+        """`rate()` for many pairs (the rating metrics' loop, cornac/eval_methods/base_method.py:35-105) in one call; pairs
+        with an unknown user or item go through `rate()` itself"""
+        u = np.asarray(user_indices, dtype=np.int64)
+        i = np.asarray(item_indices, dtype=np.int64)
+        known = (u >= 0) & (u < self.num_users) & (i >= 0) & (i < self.num_items)
+        out = np.empty(len(u), dtype=np.float64)
+        if known.any():
+            pred = self._pair_values(self._handle(), u[known], i[known])
+            out[known] = clip(pred, self.min_rating, self.max_rating) if clipping else pred
+        for p in np.flatnonzero(~known):
+            out[p] = self.rate(int(u[p]), int(i[p]), clipping)
+        return out
+
+
 adopt_reference_classes()

@@ -19,10 +19,10 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .recommender import Recommender, ScoreException, _table_fingerprint, clip
+from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint
 
 
-class VAECF(Recommender):
+class VAECF(HandleScoredRecommender):
     """Variational autoencoder for collaborative filtering.  Parameters are the reference's (recom_vaecf.py:25-79): `k` the
     size of z, `autoencoder_structure` the hidden layer `[h]`, `act_fn` in tanh / sigmoid / relu / relu6 / elu, `likelihood`
     in mult / bern / gaus / pois, `n_epochs`, `batch_size`, `learning_rate` (Adam), `beta` (the KL weight), `seed`;
@@ -104,8 +104,7 @@ class VAECF(Recommender):
         except Exception:
             model.close()
             raise
-        self._vae_handle = model   # its tables are self.vae already: kept for scoring
-        self._vae_key = self._vaecf_key()
+        self._keep_handle(model)   # its tables are self.vae already: kept for scoring
         return self
 
     # ---- the tables -------------------------------------------------------------------------------
@@ -132,76 +131,36 @@ class VAECF(Recommender):
         self.k, self.autoencoder_structure = k, [h]
         self._drop_scorer()
 
-    # ---- prediction -------------------------------------------------------------------------------
-    def _drop_scorer(self):
-        Recommender._drop_scorer(self)
-        handle = self.__dict__.pop("_vae_handle", None)
-        self.__dict__.pop("_vae_key", None)
-        self.__dict__.pop("_rank_tables", None)
-        if handle is not None:
-            handle.close()
+    # ---- prediction (recom_vaecf.py:167-202: decode(mu(x_u)), or its entry for one item) -----------
+    _HANDLE_ATTRS = ("_vae_handle", "_vae_key")   # (`_scorer` is the fused factor scorer over h2 that the orderings use)
+    _scorer_row_count = Recommender._scorer_row_count
+    batch_num_items = Recommender.batch_num_items
+    register_exclusions = Recommender.register_exclusions
 
-    def _vaecf_key(self):
+    def _drop_scorer(self):
+        HandleScoredRecommender._drop_scorer(self)
+        self.__dict__.pop("_rank_tables", None)
+
+    def _handle_key(self):
         X = self.r_mat
         return (id(X),) + tuple(_table_fingerprint(a) for a in (X.indptr, X.indices)) + tuple(
             _table_fingerprint(self.vae[n]) for n in self.NAMES)
 
-    def _vaecf_handle(self):
-        """the device handle holding r_mat and the tables: the one `fit` left, or a new one after load() / a table edit"""
-        key = self._vaecf_key()
-        if self.__dict__.get("_vae_handle") is None or self.__dict__.get("_vae_key") != key:
-            self._drop_scorer()
-            model = _lib.VaecfModel(self.r_mat, self.k, self._check_structure(), self.act_fn, self.likelihood, device=self.device)
-            try:
-                model.set_params(self.vae)
-            except Exception:
-                model.close()
-                raise
-            self._vae_handle = model
-            self._vae_key = key
-        return self._vae_handle
+    def _build_handle(self):
+        model = _lib.VaecfModel(self.r_mat, self.k, self._check_structure(), self.act_fn, self.likelihood, device=self.device)
+        try:
+            model.set_params(self.vae)
+        except Exception:
+            model.close()
+            raise
+        return model
 
     def _scoring_tables(self):
         """(h2 of every user at z = mu, D1, c1, zeros): the decoder's logits as a factor model"""
-        handle = self._vaecf_handle()
+        handle = self._handle()
         cached = self.__dict__.get("_rank_tables")
         if cached is None or cached[0] != self._vae_key:
             H2 = handle.encode_users(np.arange(self.num_users, dtype=np.int32))
             cached = (self._vae_key, (H2, self.vae[self.NAMES[8]], self.vae[self.NAMES[9]], np.zeros(self.num_users, np.float32)))
             self._rank_tables = cached
         return cached[1]
-
-    def _unknown(self, user_idx, item_idx):
-        # recom_vaecf.py:185-189
-        if self.is_unknown_user(user_idx):
-            raise ScoreException("Can't make score prediction for user %d" % user_idx)
-        if item_idx is not None and self.is_unknown_item(item_idx):
-            raise ScoreException("Can't make score prediction for item %d" % item_idx)
-
-    def score(self, user_idx, item_idx=None):
-        """recom_vaecf.py:167-202: decode(mu(x_u)), or its entry for one item"""
-        self._unknown(user_idx, item_idx)
-        handle = self._vaecf_handle()
-        if item_idx is not None:
-            return handle.score_pairs([user_idx], [item_idx])[0]
-        return handle.score_users([user_idx])[0]
-
-    def score_batch(self, user_indices):
-        """`score(u)` for every listed user in one call: [n, num_items] float32"""
-        users = np.asarray(user_indices, dtype=np.int64).ravel()
-        for u in users:
-            self._unknown(int(u), None)
-        return self._vaecf_handle().score_users(users)
-
-    def rate_batch(self, user_indices, item_indices, clipping=True):
-        """`rate()` for many pairs in one call, on probabilities; pairs with an unknown user or item go through `rate()`"""
-        u = np.asarray(user_indices, dtype=np.int64)
-        i = np.asarray(item_indices, dtype=np.int64)
-        known = (u >= 0) & (u < self.num_users) & (i >= 0) & (i < self.num_items)
-        out = np.empty(len(u), dtype=np.float64)
-        if known.any():
-            pred = self._vaecf_handle().score_pairs(u[known], i[known])
-            out[known] = clip(pred, self.min_rating, self.max_rating) if clipping else pred
-        for p in np.flatnonzero(~known):
-            out[p] = self.rate(int(u[p]), int(i[p]), clipping)
-        return out

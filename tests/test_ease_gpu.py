@@ -218,6 +218,29 @@ def test_scoring_edges_bit_for_bit():
     assert ec.same_bits(pairs, np.array([ec.score_pair(X, B, int(u), int(i)) for u, i in zip(pu, pi)]))
 
 
+def test_more_ids_than_one_chunk_holds():
+    """the chunk loop past its first chunk (b0 > 0).  score_users takes min(65535, 256 MiB / (8 n_items)) users per chunk:
+    65 535 at 4 items (256 MiB / 32 bytes is about 8 million), so 65 536 ids make a second chunk of one; score_pairs takes
+    2^20 pairs per chunk, so 2^20 + 1 do the same"""
+    import scipy.sparse as sp
+
+    n_users, n_items = 3, 4
+    X = sp.csr_matrix(np.array([[1.0, 0.0, 2.5, 0.0], [0.0, 0.0, 0.0, 0.0], [0.5, 3.0, 0.0, 4.0]]))
+    B = np.random.RandomState(23).uniform(-1.0, 1.0, (n_items, n_items))
+    user_cap, pair_cap = min(65535, (256 << 20) // (8 * n_items)), 1 << 20
+    nu, npairs = 65536, (1 << 20) + 1
+    assert nu > user_cap and npairs > pair_cap, "more than one chunk's worth"
+    want_rows = np.array([ec.score_user(X, B, u) for u in range(n_users)])
+    want_pairs = np.array([[ec.score_pair(X, B, u, i) for i in range(n_items)] for u in range(n_users)])
+    users = np.arange(nu) % n_users
+    pu, pi = np.arange(npairs) % n_users, (np.arange(npairs) // n_users) % n_items
+    with handle(X) as m:
+        m.set_table(B)
+        rows, pairs = m.score_users(users), m.score_pairs(pu, pi)
+    assert rows.shape == (nu, n_items) and ec.same_bits(rows, want_rows[users])
+    assert pairs.shape == (npairs,) and ec.same_bits(pairs, want_pairs[pu, pi])
+
+
 # ---- end to end ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(ec.CONFIGS))
 def test_end_to_end(golden, name, tmp_path):

@@ -186,6 +186,26 @@ def test_batches_of_1_and_65_with_a_repeated_user(golden):
         sc.close()
 
 
+def test_more_pairs_than_one_chunk_holds(golden):
+    """the chunk loop past its first chunk (b0 > 0): a chunk's dense rows of Q take at most 64 MiB, 8 n_neighbours bytes per
+    id, which is 55 924 ids at 150 neighbours, so one more pair makes a second chunk of one.  (score_users shares the loop;
+    that many users there would be millions of one-wave workgroups.)"""
+    g = golden_case(golden, "B/user_cosine")
+    N, Q, user_mode = kc.tables("user", g["sim"], g["rat"])
+    n_items, n_neighbours, n_users = N.shape[0], N.shape[1], Q.shape[0]
+    cap = (64 << 20) // (8 * n_neighbours)
+    n = cap + 1
+    assert n > cap >= 1, "more than one chunk's worth"
+    pu, pi = np.arange(n) % n_users, (np.arange(n) // n_users) % n_items
+    sc = _lib.KnnScorer(N, Q, user_mode)
+    try:
+        everyone = sc.score_users(np.arange(n_users), 20)
+        pairs = sc.score_pairs(pu, pi, 20)
+    finally:
+        sc.close()
+    assert pairs.shape == (n,) and np.array_equal(pairs.view(np.uint64), everyone[pu, pi].view(np.uint64))
+
+
 # ---- end to end --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(kc.CONFIGS))
 def test_fit_and_score_against_the_golden(golden, name):

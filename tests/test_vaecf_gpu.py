@@ -187,6 +187,24 @@ def test_scores_against_the_restatement_and_the_golden(golden, name):
         assert (p[start.B > 0] < 1e-6).any(), "the saturated case: some held item has p < 1e-6"
 
 
+def test_more_ids_than_one_chunk_holds(golden):
+    """the chunk loop past its first chunk (b0 > 0): the entry points take min(1024, 256 MiB / (4 n_items)) users per chunk,
+    which is 1024 at 131 items (256 MiB / 524 bytes is about 512 000), so 1 025 ids make a second chunk of one"""
+    name = min(vc.FULL_CASES, key=lambda n: (vc.CASES[n]["nu"] * vc.CASES[n]["ni"], vc.FULL_CASES.index(n)))
+    c = vc.CASES[name]
+    cap = min(1024, (256 << 20) // (4 * c["ni"]))
+    n = 1025
+    assert n > cap, "more than one chunk's worth"
+    params = {p: golden["%s/P/%s" % (name, vc.SHORT[p])] for p in vc.NAMES}
+    users, items = np.arange(n) % c["nu"], np.arange(n) % c["ni"]
+    with handle(name, params) as m:
+        everyone, codes = m.score_users(np.arange(c["nu"])), m.encode_users(np.arange(c["nu"]))
+        rows, h2, pairs = m.score_users(users), m.encode_users(users), m.score_pairs(users, items)
+    assert rows.shape == (n, c["ni"]) and np.array_equal(rows.view(np.uint32), everyone[users].view(np.uint32))
+    assert h2.shape == (n, c["h"]) and np.array_equal(h2.view(np.uint32), codes[users].view(np.uint32))
+    assert pairs.shape == (n,) and np.array_equal(pairs.view(np.uint32), everyone[users, items].view(np.uint32))
+
+
 def test_rank_batch_is_the_sort_of_score_batch(golden):
     """encode_users + the fused scorer on logits against sorting the probabilities, where these do not tie"""
     name = "i257"
