@@ -27,8 +27,10 @@ constexpr int kBlk = 256;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float v4f32 __attribute__((ext_vector_type(4)));
 
+// (-0.0 and +0.0 are one score — the oracle's stable argsort ties them — so both get the key of +0.0: x + 0.0f is +0.0 for
+// either zero and x for everything else, subnormals included)
 __device__ __forceinline__ uint32_t order_key(float s) {
-    const uint32_t b = __float_as_uint(s);
+    const uint32_t b = __float_as_uint(s + 0.0f);
     const uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     return k ? k : 1u;
 }
@@ -358,7 +360,8 @@ __global__ __launch_bounds__(kBlk, ((KT <= 32 || CAP <= 42) ? 2 : 1)) void rank_
                 unsigned long long mine = lane < c ? krow[lane] : 0ull;
                 if (excl_indptr && !excl_bits) {  // no bitmap (huge catalogue): drop excluded items before they can raise the threshold
                     bool dropped = false;
-                    if (mine != 0ull) {
+                    // (a row beyond n_rows has no list; it can hold candidates all the same: +inf >= its +inf threshold)
+                    if (mine != 0ull && row_tile * 32 + rl < n_rows) {
                         const int32_t item = (int32_t)(uint32_t)mine;
                         const int64_t grow = excl_row0 + row_tile * 32 + rl;
                         int64_t lo = excl_indptr[grow], hi = excl_indptr[grow + 1];
@@ -1182,6 +1185,7 @@ static bool can_fuse(cornac_hip_scorer_t h, int topk) { return topk <= kFusedMax
 
 // fused GEMM + top-k for rows [0, n): users from d_users (or u0 + row); optional exclusion CSR on the device
 constexpr int64_t kMaxBitmapTiles = 8192;  // item tiles (x32 items) up to which the exclusion bitmap is used
+constexpr int64_t kMergeMaxKeys = 16384;   // keys (8 bytes each) of rank_merge_kernel's LDS list: 128 KB of the 160 KB
 
 // excl_by_user: d_excl_indptr is indexed by user id (resident lists) instead of by row of this call
 static void launch_rank_fused_rows(cornac_hip_scorer_t h, const int32_t *d_users, int64_t u0, int64_t n, int topk,
@@ -1198,6 +1202,9 @@ static void launch_rank_fused_rows(cornac_hip_scorer_t h, const int32_t *d_users
     const int64_t work_total = wg_rows * n_item_tiles;
     int64_t work_per_wg = std::max<int64_t>((work_total + (int64_t)di.cus * wgs_per_cu - 1) / ((int64_t)di.cus * wgs_per_cu),
                                             std::min<int64_t>(16, n_item_tiles));
+    // rank_merge_kernel sorts the max_segs x topk keys of a row in LDS, padded to a power of two: at most kMergeMaxKeys
+    // (one row block over 262 144 items is 513 segments on 256 CUs; x 32 keys that would be a 256 KB list)
+    work_per_wg = std::max<int64_t>(work_per_wg, (n_item_tiles + (kMergeMaxKeys / topk - 1) - 1) / (kMergeMaxKeys / topk - 1));
     const int64_t n_wgs = (work_total + work_per_wg - 1) / work_per_wg;
     const int64_t max_segs = (n_item_tiles + work_per_wg - 1) / work_per_wg + 1;
     h->part.ensure((size_t)(max_segs * n * topk));
