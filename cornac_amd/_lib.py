@@ -59,7 +59,7 @@ SYMBOLS = [
     "cornac_hip_wmf_fit_batches", "cornac_hip_wmf_kernel_timing", "cornac_hip_wmf_last_timing",
     "cornac_hip_mf_create", "cornac_hip_mf_destroy", "cornac_hip_mf_set_factors", "cornac_hip_mf_get_factors",
     "cornac_hip_mf_fit", "cornac_hip_mf_bind_items", "cornac_hip_mf_bind_users", "cornac_hip_mf_set_stream", "cornac_hip_mf_epoch_enqueue",
-    "cornac_hip_mf_sync", "cornac_hip_mf_fit_sgd", "cornac_hip_mf_last_timing",
+    "cornac_hip_mf_sync", "cornac_hip_mf_fit_sgd", "cornac_hip_mf_last_timing", "cornac_hip_mf_det_form",
     "cornac_hip_mf_hogwild_form", "cornac_hip_mf_hogwild_stats", "cornac_hip_mf_debug_split", "cornac_hip_mf_debug_ownership",
     "cornac_hip_mf_fit_minibatch", "cornac_hip_mf_fit_minibatch_dropout", "cornac_hip_mf_reset_optimizer",
     "cornac_hip_mf_pmf_set_factors", "cornac_hip_mf_pmf_get_factors", "cornac_hip_mf_pmf_fit", "cornac_hip_mf_pmf_form",
@@ -245,6 +245,7 @@ def lib():
         L.cornac_hip_mf_pmf_get_factors.argtypes = [_vp, _vp, _vp]
         L.cornac_hip_mf_pmf_fit.argtypes = [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _vp]
         L.cornac_hip_mf_pmf_form.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cornac_hip_mf_det_form.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cornac_hip_mf_nmf_set_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
         L.cornac_hip_mf_nmf_get_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
         L.cornac_hip_mf_nmf_fit.argtypes = [_vp, C.c_int] + [C.c_float] * 6 + [C.c_int, C.c_int, _vp]
@@ -780,6 +781,13 @@ class MfTrainer(_HandleOwner):
         check(lib().cornac_hip_mf_fit(self.h, max_iter, lr, reg, mu, int(use_bias), int(early_stop), mode,
                                       loss.ctypes.data, C.byref(n)))
         return loss[:n.value], n.value
+
+    def det_form(self):
+        """(form, own_user) of the last deterministic epoch: 1 dataflow launch / 2 level schedule / 0 none yet; whether the
+        dataflow launch's waves owned the user rows (0 unless form is 1)"""
+        form, own = C.c_int(), C.c_int()
+        check(lib().cornac_hip_mf_det_form(self.h, C.byref(form), C.byref(own)))
+        return form.value, own.value
 
     # ---- multi-GPU driver surface (cornac_amd/dist.py ShardedMfTrainer) ----------------------------------------
     def bind_items(self, d_V, d_Bi):

@@ -12,8 +12,8 @@
 //   nmf_bias_level_kernel  use_bias: one launch per level of the row-conflict schedule (mf_build_schedule's levels) —
 //                          below 4096 ratings and after a refused cooperative launch.  Also the plain r_pred pass of
 //                          k > 256 without biases (one launch over all ratings).
-//   nmf_bias_chain_kernel  use_bias, from 4096 ratings: the schedule of mf_det_chain_kernel (one persistent dataflow
-//                          launch), users owned — a user's ratings are adjacent in the CSR and its Bu stays with one wave
+//   nmf_bias_chain_kernel  use_bias, from 4096 ratings: the dataflow driver of chain.h (one persistent launch; the
+//                          protocol is explained there), users owned — a user's ratings are adjacent in the CSR and its Bu stays with one wave
 //                          — the item bias handed over by version counters with system-scope loads and stores.  U and V
 //                          are frozen, so the per-rating body is the serial dot plus scalars, any k; it stores r_pred[j].
 //                          Sequential-exact in both modes.
@@ -250,15 +250,7 @@ __global__ __launch_bounds__(kBlock) void nmf_bias_level_kernel(const int32_t *_
 }
 
 struct NmfChainArgs {
-    const int64_t *wrow_ptr;        // [W + 1] rows (users) of wave w
-    const int32_t *row_id;          // the user of a row
-    const int64_t *row_end;         // end of the user's ratings — CSR positions: a row's cursor IS the stored index j
-    int64_t *row_cur;
-    const int32_t *csid, *cseq;     // [j] item, position of j among the item's ratings
-    const float *cr;                // [j] rating
-    unsigned int *ver;              // [items] finished ratings of the item in this epoch
-    unsigned int *abort;
-    long long wait_bound_ticks;
+    ChainArgs c;   // rows = users, csid / cseq / cr = the CSR's items, positions inside the item, ratings: a position IS the stored index j
     const float *U, *V;
     float *Bu, *Bi, *pred;
     double *loss_acc;
@@ -266,110 +258,33 @@ struct NmfChainArgs {
     float lr, lbu, lbi, mu;
 };
 
-// the schedule of pmf_det_chain_kernel (64 / G ready ratings per pass, one per lane group), users owned
+// 64 / G ready ratings per pass, one per lane group (as pmf_det_chain_kernel), users owned
 template <int G>
 __global__ __launch_bounds__(kBlock) void nmf_bias_chain_kernel(const NmfChainArgs a) {
-    constexpr int TPW = kWave / G;
-    const int lane = lane_id();
-    const int grp = lane / G, lg = lane & (G - 1);
-    const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t q0 = a.wrow_ptr[w], q1 = a.wrow_ptr[w + 1];
     const int k = a.k;
     double err2 = 0.0;
-    unsigned long long t_idle = 0;  // real-time stamp of the first fruitless sweep in a row (0: progressing)
-    unsigned int idle_sweeps = 0;
-    bool give_up = false;
-    while (!give_up) {
-        bool unfinished = false, progressed = false;
-        for (int64_t base = q0; base < q1; base += kWave) {
-            const int64_t q = base + lane;
-            const bool mine = q < q1;
-            int64_t cur = mine ? a.row_cur[q] : 0;
-            const int64_t rend = mine ? a.row_end[q] : 0;
-            const int32_t oid = mine ? a.row_id[q] : 0;
-            for (;;) {
-                // ---- poll the next rating of up to 64 users at once ----
-                const bool has = mine && cur < rend;
-                const int32_t sid = has ? a.csid[cur] : 0;
-                const unsigned int seq = has ? (unsigned int)a.cseq[cur] : 0u;
-                const unsigned int v = has ? __hip_atomic_load(a.ver + sid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : ~0u;
-                unsigned long long ready = __ballot(has && v == seq);
-                if (!ready) break;
-                asm volatile("" ::: "memory");  // (compiler: the loads below stay behind the poll; the hardware issues in order)
-                progressed = true;
-                const float rr = has ? a.cr[cur] : 0.f;
-                while (ready) {
-                    // ---- this pass: the next ready ratings, one per lane group ----
-                    int l = lane;
-                    bool act = false;
-                    unsigned long long taken = 0ull;
-#pragma unroll
-                    for (int g = 0; g < TPW; ++g) {
-                        if (ready) {
-                            const int lj = __builtin_ctzll(ready);
-                            ready &= ready - 1;
-                            taken |= 1ull << lj;
-                            if (grp == g) {
-                                l = lj;
-                                act = true;
-                            }
-                        }
-                    }
-                    const int32_t u = __shfl(oid, l, kWave), i = __shfl(sid, l, kWave);
-                    const unsigned int sq = (unsigned int)__shfl((int)seq, l, kWave);
-                    const float r = __shfl(rr, l, kWave);
-                    const int32_t j = __shfl((int32_t)cur, l, kWave);
-                    const float *pu = a.U + (size_t)u * k, *pi = a.V + (size_t)i * k;
-                    const float bu = act ? a.Bu[u] : 0.f, bi = act ? load_f32_sys(a.Bi + i) : 0.f;
-                    // ---- the reference's expression tree (nmf_bias_level_kernel) ----
-                    float pred = a.mu + bu + bi;
-                    for (int fb = 0; fb < k; fb += G) {
-                        const int f = fb + lg;
-                        float p = 0.f;
-                        if (act && f < k) p = pu[f] * pi[f];
-                        pred = ordered_lane_sum<G>(pred, p, min(G, k - fb));
-                    }
-                    const float err = r - pred;
-                    if (act && lg == 0) {
-                        a.pred[j] = pred;
-                        a.Bu[u] = bu + a.lr * (err - a.lbu * bu);
-                        store_f32_sys(a.Bi + i, bi + a.lr * (err - a.lbi * bi));
-                        err2 += (double)(err * err);
-                    }
-                    // ---- publish: every store of this wave has left before any of its counters moves ----
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (act && lg == 0) __hip_atomic_store(a.ver + i, sq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    if ((taken >> lane) & 1ull) ++cur;
-                }
-            }
-            if (mine) a.row_cur[q] = cur;
-            unfinished = unfinished || __ballot(mine && cur < rend) != 0ull;
+    chain_run<G>(a.c, [&](const ChainPass p) {
+        const int32_t u = p.oid, i = p.sid;
+        const float *pu = a.U + (size_t)u * k, *pi = a.V + (size_t)i * k;
+        const float bu = p.act ? a.Bu[u] : 0.f, bi = p.act ? load_f32_sys(a.Bi + i) : 0.f;
+        // ---- the reference's expression tree (nmf_bias_level_kernel) ----
+        float pred = a.mu + bu + bi;
+        for (int fb = 0; fb < k; fb += G) {
+            const int f = fb + p.lg;
+            float x = 0.f;
+            if (p.act && f < k) x = pu[f] * pi[f];
+            pred = ordered_lane_sum<G>(pred, x, min(G, k - fb));
         }
-        if (!unfinished) break;
-        if (progressed) {
-            t_idle = 0;
-            idle_sweeps = 0;
-            continue;
+        const float err = p.r - pred;
+        if (p.act && p.lg == 0) {
+            a.pred[p.pos] = pred;
+            a.Bu[u] = bu + a.lr * (err - a.lbu * bu);
+            store_f32_sys(a.Bi + i, bi + a.lr * (err - a.lbi * bi));
+            err2 += (double)(err * err);
         }
-        // nothing of this wave can run yet: back off (longer the longer it lasts) and watch the bound
-        ++idle_sweeps;
-        if (idle_sweeps < 8) __builtin_amdgcn_s_sleep(8);
-        else if (idle_sweeps < 64) __builtin_amdgcn_s_sleep(64);
-        else __builtin_amdgcn_s_sleep(127);
-        if ((idle_sweeps & 255u) == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t_idle == 0) t_idle = now;
-            int bad = 0;
-            if (lane == 0 && (now - t_idle > (unsigned long long)a.wait_bound_ticks ||
-                              __hip_atomic_load(a.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM))) {
-                if (atomicCAS(a.abort, 0u, 1u) == 0u) a.abort[1] = (unsigned int)w;
-                bad = 1;
-            }
-            give_up = __builtin_amdgcn_readfirstlane(bad) != 0;
-        }
-    }
+    });
     const double l = wave_sum_f64(err2);
-    if (lane == 0 && l != 0.0) atomicAdd(a.loss_acc, l);
+    if (lane_id() == 0 && l != 0.0) atomicAdd(a.loss_acc, l);
 }
 
 }  // namespace chip
@@ -504,53 +419,27 @@ static void nmf_build_plan(cornac_hip_mf_t h, int mode) {
     pl.built = true;
 }
 
-// the dataflow plan of the bias pass: users onto waves, heaviest first onto the least loaded wave; a wave's users in CSR
-// order.  Returns false where the occupancy query admits fewer than two workgroups per CU.
+// the dataflow plan of the bias pass: users onto waves (chain_deal; a wave's users in CSR order), their CSR ranges as the
+// rows' ratings.  Returns false where the occupancy query admits fewer than two workgroups per CU.
 static bool nmf_build_chain(cornac_hip_mf_t h) {
-    if (h->nmf_chain_built) return h->nmf_chain_grid > 0;
+    if (h->nmf_chain_built) return h->nmf_chain.grid > 0;
     h->nmf_chain_built = true;
     int per_cu = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pick_nmf_chain_kernel(h->k), kBlock, 0));
     if (per_cu < 2) return false;   // half of an answer of 1 would be the whole admitted grid: the level schedule instead
     // half of what the query admits (mf_build_chain: every block of the grid stays resident)
     const int grid = device_info(h->device).cus * (std::min(per_cu, 8) / 2);
-    const int64_t W = (int64_t)grid * kWavesPerBlock, nu = h->n_users;
     const std::vector<int64_t> &uptr = h->nmf_uptr_h;
-    std::vector<int32_t> order((size_t)nu);
-    for (int64_t u = 0; u < nu; ++u) order[(size_t)u] = (int32_t)u;
-    auto cnt = [&](int32_t u) { return uptr[(size_t)u + 1] - uptr[(size_t)u]; };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cnt(x) > cnt(y); });
-    typedef std::pair<int64_t, int64_t> LW;
-    std::priority_queue<LW, std::vector<LW>, std::greater<LW>> heap;
-    for (int64_t w = 0; w < W; ++w) heap.push(LW(0, w));
-    std::vector<std::vector<int32_t>> wrows((size_t)W);
-    for (int32_t u : order) {
-        if (cnt(u) == 0) continue;
-        LW top = heap.top();
-        heap.pop();
-        wrows[(size_t)top.second].push_back(u);
-        top.first += cnt(u);
-        heap.push(top);
-    }
-    std::vector<int64_t> wrow_ptr((size_t)W + 1, 0), row_beg, row_end;
+    std::vector<int64_t> cnt((size_t)h->n_users), wrow_ptr;
+    for (int64_t u = 0; u < h->n_users; ++u) cnt[(size_t)u] = uptr[(size_t)u + 1] - uptr[(size_t)u];
     std::vector<int32_t> row_id;
-    for (int64_t w = 0; w < W; ++w) {
-        std::sort(wrows[(size_t)w].begin(), wrows[(size_t)w].end());
-        for (int32_t u : wrows[(size_t)w]) {
-            row_id.push_back(u);
-            row_beg.push_back(uptr[(size_t)u]);
-            row_end.push_back(uptr[(size_t)u + 1]);
-        }
-        wrow_ptr[(size_t)w + 1] = (int64_t)row_id.size();
+    chain_deal(cnt, uptr, (int64_t)grid * kWavesPerBlock, wrow_ptr, row_id);
+    std::vector<int64_t> row_beg(row_id.size()), row_end(row_id.size());
+    for (size_t q = 0; q < row_id.size(); ++q) {
+        row_beg[q] = uptr[(size_t)row_id[q]];
+        row_end[q] = uptr[(size_t)row_id[q] + 1];
     }
-    nmf_put(h->nmf_c_wrow_ptr, wrow_ptr, h->stream); nmf_put(h->nmf_c_row_id, row_id, h->stream);
-    nmf_put(h->nmf_c_row_beg, row_beg, h->stream); nmf_put(h->nmf_c_row_end, row_end, h->stream);
-    h->nmf_c_row_cur.alloc(std::max<size_t>(row_id.size(), 1));
-    h->nmf_c_rows = row_id.size();
-    h->nmf_ver.alloc((size_t)h->n_items);
-    h->nmf_abort.alloc(8);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->nmf_chain_grid = grid;
+    chain_upload(h->nmf_chain, grid, wrow_ptr, row_id, row_beg, row_end, h->n_items, h->stream);
     return true;
 }
 
@@ -560,31 +449,11 @@ struct NmfHyper {
 
 // false when the runtime refuses the cooperative launch (nothing has run)
 static bool nmf_bias_chain(cornac_hip_mf_t h, const NmfHyper &hy, double *loss_slot) {
-    HIP_CHECK(hipMemsetAsync(h->nmf_ver.p, 0, h->nmf_ver.n * sizeof(unsigned int), h->stream));
-    HIP_CHECK(hipMemsetAsync(h->nmf_abort.p, 0, 8 * sizeof(unsigned int), h->stream));
-    if (h->nmf_c_rows)
-        HIP_CHECK(hipMemcpyAsync(h->nmf_c_row_cur.p, h->nmf_c_row_beg.p, h->nmf_c_rows * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
     NmfChainArgs a;
-    a.wrow_ptr = h->nmf_c_wrow_ptr.p; a.row_id = h->nmf_c_row_id.p; a.row_end = h->nmf_c_row_end.p; a.row_cur = h->nmf_c_row_cur.p;
-    a.csid = h->nmf_cid.p; a.cseq = h->nmf_cseq.p; a.cr = h->val.p;
-    a.ver = h->nmf_ver.p; a.abort = h->nmf_abort.p;
-    a.wait_bound_ticks = (long long)prof_env_int("CORNAC_HIP_MF_CHAIN_WAIT_S", 120) * 100000000ll;
+    a.c = chain_args(h->nmf_chain, h->nmf_cid.p, h->nmf_cseq.p, h->val.p);
     a.U = h->nmf_U.p; a.V = h->nmf_V.p; a.Bu = h->nmf_Bu.p; a.Bi = h->nmf_Bi.p; a.pred = h->nmf_pred.p; a.loss_acc = loss_slot;
     a.k = h->k; a.lr = hy.lr; a.lbu = hy.lambda_bu; a.lbi = hy.lambda_bi; a.mu = hy.mu;
-    void *kargs[] = {(void *)&a};
-    const hipError_t st = hipLaunchCooperativeKernel((const void *)pick_nmf_chain_kernel(h->k), dim3(h->nmf_chain_grid), dim3(kBlock),
-                                                     kargs, 0, h->stream);
-    if (st == hipErrorCooperativeLaunchTooLarge) {
-        (void)hipGetLastError();
-        return false;
-    }
-    HIP_CHECK(st);
-    unsigned int ab[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(ab, h->nmf_abort.p, sizeof ab, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (ab[0])
-        fail(CORNAC_HIP_ERR_HIP, "NMF bias dataflow kernel: wave %u made no progress for its time bound (internal error)", ab[1]);
-    return true;
+    return chain_launch(h->stream, h->nmf_chain, pick_nmf_chain_kernel(h->k), &a, "NMF bias dataflow kernel");
 }
 
 static void nmf_launch_level(cornac_hip_mf_t h, const int32_t *lpos, int64_t off, int cnt, const NmfHyper &hy, int use_bias,

@@ -16,29 +16,20 @@
 //
 //   pmf_det_level_kernel  one launch per level of the row-conflict DAG (mf_build_schedule): k > 256, nnz < 4096, and after
 //                         a refused cooperative launch
-//   pmf_det_chain_kernel  the schedule of mf_det_chain_kernel (mf.hip: one persistent dataflow launch, owned rows in stored
-//                         order by one wave, shared rows handed over by version counters) with this per-rating body and
-//                         four float64 tables: the shared side's parameter row AND its cache row travel with system-scope
-//                         8-byte loads and stores, the owned side's with plain ones.
+//   pmf_det_chain_kernel  the dataflow driver of chain.h (one persistent launch, owned rows in stored order by one wave,
+//                         shared rows handed over by version counters: the protocol is explained there) on MF's plan, with
+//                         this per-rating body and four float64 tables: the shared side's parameter row AND its cache row
+//                         travel with system-scope 8-byte loads and stores, the owned side's with plain ones.
 //
 // Several ratings per wave pass (G < 64).  PMF's default is k = 5: one rating per wave would leave 59 lanes idle on a
-// latency-bound kernel.  The ratings one poll finds ready are mutually independent: their owned rows are distinct (one per
-// lane), and so are their shared rows — two ratings of one shared row carry different cseq, and only one can equal ver.  So
-// for k <= 32 the ready set runs in lane groups of G = pow2 >= k (8, 16, 32 lanes: 8, 4, 2 ratings per pass); each group
-// does its own ordered sum and publishes its own ver after the wave's stores have drained.
+// latency-bound kernel.  The ratings one poll finds ready are mutually independent (chain.h), so for k <= 32 the ready
+// set runs in lane groups of G = pow2 >= k (8, 16, 32 lanes: 8, 4, 2 ratings per pass).
 
 namespace chip {
 
 struct PmfHyper {
     double lr, reg, gamma, one_minus_gamma;  // the reference's float arguments (and its float 1 - gamma), promoted
 };
-
-__device__ __forceinline__ double load_f64_sys(const double *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void store_f64_sys(double *p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // expf(x), |x| <= 6, the way the host's libm evaluates it (glibc >= 2.27, the scheme of Arm's optimized routines): all in
 // double — x 32 / ln2 = k + r with k integer and |r| <= 1/2 (the add-and-subtract of 1.5 x 2^52 rounds to nearest even),
@@ -121,12 +112,6 @@ __device__ __forceinline__ double pmf_ordered_sum(double acc, double p, int lim)
     return ordered_lane_sum_t<G>(acc, p, lim);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
 template <int G, int VARIANT>
 __global__ __launch_bounds__(kBlock) void pmf_det_level_kernel(const int32_t *__restrict__ ou, const int32_t *__restrict__ oi,
                                                                const float *__restrict__ orat, int64_t off, int cnt, double *U,
@@ -168,15 +153,7 @@ __global__ __launch_bounds__(kBlock) void pmf_det_level_kernel(const int32_t *__
 }
 
 struct PmfChainArgs {
-    const int64_t *wrow_ptr;        // the plan of mf_build_chain (MfChainArgs)
-    const int32_t *row_id;
-    const int64_t *row_end;
-    int64_t *row_cur;
-    const int32_t *csid, *cseq;
-    const float *cr;
-    unsigned int *ver;
-    unsigned int *abort;
-    long long wait_bound_ticks;
+    ChainArgs c;                    // the plan of mf_build_chain
     double *U, *V, *CU, *CV;
     double *loss_acc;
     int k;
@@ -187,149 +164,54 @@ struct PmfChainArgs {
 template <int G, int R, bool OWN_USER, int VARIANT>
 __global__ __launch_bounds__(kBlock) void pmf_det_chain_kernel(const PmfChainArgs a) {
     static_assert(G == kWave || R == 1, "lane groups hold a whole row");
-    constexpr int TPW = kWave / G;
-    const int lane = lane_id();
-    const int grp = lane / G, lg = lane & (G - 1);
-    const int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-    const int64_t q0 = a.wrow_ptr[w], q1 = a.wrow_ptr[w + 1];
     double err2 = 0.0, nrm = 0.0;
-    unsigned long long t_idle = 0;  // real-time stamp of the first fruitless sweep in a row (0: progressing)
-    unsigned int idle_sweeps = 0;
-    bool give_up = false;
-    while (!give_up) {
-        bool unfinished = false, progressed = false;
-        for (int64_t base = q0; base < q1; base += kWave) {
-            const int64_t q = base + lane;
-            const bool mine = q < q1;
-            int64_t cur = mine ? a.row_cur[q] : 0;
-            const int64_t rend = mine ? a.row_end[q] : 0;
-            const int32_t oid = mine ? a.row_id[q] : 0;
-            for (;;) {
-                // ---- poll the next rating of up to 64 rows at once ----
-                const bool has = mine && cur < rend;
-                const int32_t sid = has ? a.csid[cur] : 0;
-                const unsigned int seq = has ? (unsigned int)a.cseq[cur] : 0u;
-                const unsigned int v = has ? __hip_atomic_load(a.ver + sid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : ~0u;
-                unsigned long long ready = __ballot(has && v == seq);
-                if (!ready) break;
-                asm volatile("" ::: "memory");  // (compiler: the row loads below stay behind the poll; the hardware issues in order)
-                progressed = true;
-                const float rr = has ? a.cr[cur] : 0.f;
-                while (ready) {
-                    // ---- this pass: the next ready rating (one per lane group) ----
-                    int l = lane;
-                    bool act = false;
-                    unsigned long long taken = 0ull;
-                    if (TPW == 1) {
-                        l = __builtin_ctzll(ready);
-                        ready &= ready - 1;
-                        taken = 1ull << l;
-                        act = true;
-                    } else {
+    chain_run<G>(a.c, [&](const ChainPass p) {
+        const int32_t u = OWN_USER ? p.oid : p.sid, i = OWN_USER ? p.sid : p.oid;
+        double *pu = a.U + (size_t)u * a.k, *pi = a.V + (size_t)i * a.k;
+        double *pcu = a.CU + (size_t)u * a.k, *pcv = a.CV + (size_t)i * a.k;
+        double uf[R], vf[R], cu[R], cv[R];
 #pragma unroll
-                        for (int j = 0; j < TPW; ++j) {
-                            if (ready) {
-                                const int lj = __builtin_ctzll(ready);
-                                ready &= ready - 1;
-                                taken |= 1ull << lj;
-                                if (grp == j) {
-                                    l = lj;
-                                    act = true;
-                                }
-                            }
-                        }
-                    }
-                    int32_t o, s;
-                    unsigned int sq;
-                    float r;
-                    if (TPW == 1) {
-                        o = __builtin_amdgcn_readlane(oid, l);
-                        s = __builtin_amdgcn_readlane(sid, l);
-                        sq = (unsigned int)__builtin_amdgcn_readlane((int)seq, l);
-                        r = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rr), l));
-                    } else {
-                        o = __shfl(oid, l, kWave);
-                        s = __shfl(sid, l, kWave);
-                        sq = (unsigned int)__shfl((int)seq, l, kWave);
-                        r = __shfl(rr, l, kWave);
-                    }
-                    const int32_t u = OWN_USER ? o : s, i = OWN_USER ? s : o;
-                    double *pu = a.U + (size_t)u * a.k, *pi = a.V + (size_t)i * a.k;
-                    double *pcu = a.CU + (size_t)u * a.k, *pcv = a.CV + (size_t)i * a.k;
-                    double uf[R], vf[R], cu[R], cv[R];
+        for (int c = 0; c < R; ++c) {
+            const int f = p.lg + G * c;
+            const bool in = p.act && f < a.k;
+            uf[c] = in ? (OWN_USER ? pu[f] : load_f64_sys(pu + f)) : 0.0;
+            vf[c] = in ? (OWN_USER ? load_f64_sys(pi + f) : pi[f]) : 0.0;
+            cu[c] = in ? (OWN_USER ? pcu[f] : load_f64_sys(pcu + f)) : 0.0;
+            cv[c] = in ? (OWN_USER ? load_f64_sys(pcv + f) : pcv[f]) : 0.0;
+        }
+        // ---- the reference's expression tree (pmf_det_level_kernel) ----
+        double dot = 0.0;
 #pragma unroll
-                    for (int c = 0; c < R; ++c) {
-                        const int f = lg + G * c;
-                        const bool in = act && f < a.k;
-                        uf[c] = in ? (OWN_USER ? pu[f] : load_f64_sys(pu + f)) : 0.0;
-                        vf[c] = in ? (OWN_USER ? load_f64_sys(pi + f) : pi[f]) : 0.0;
-                        cu[c] = in ? (OWN_USER ? pcu[f] : load_f64_sys(pcu + f)) : 0.0;
-                        cv[c] = in ? (OWN_USER ? load_f64_sys(pcv + f) : pcv[f]) : 0.0;
-                    }
-                    // ---- the reference's expression tree (pmf_det_level_kernel) ----
-                    double dot = 0.0;
+        for (int c = 0; c < R; ++c) {
+            if (G * c < a.k) dot = pmf_ordered_sum<G>(dot, uf[c] * vf[c], min(G, a.k - G * c));
+        }
+        double e, wt;
+        pmf_errors<VARIANT>((double)p.r, dot, e, wt);
 #pragma unroll
-                    for (int c = 0; c < R; ++c) {
-                        if (G * c < a.k) dot = pmf_ordered_sum<G>(dot, uf[c] * vf[c], min(G, a.k - G * c));
-                    }
-                    double e, wt;
-                    pmf_errors<VARIANT>((double)r, dot, e, wt);
-#pragma unroll
-                    for (int c = 0; c < R; ++c) {
-                        const int f = lg + G * c;
-                        if (act && f < a.k) {
-                            double un = uf[c], cun = cu[c], vn = vf[c], cvn = cv[c];
-                            pmf_row_step(wt, vf[c], un, cun, a.hy);
-                            pmf_row_step(wt, un, vn, cvn, a.hy);
-                            if (OWN_USER) {
-                                pu[f] = un;
-                                pcu[f] = cun;
-                                store_f64_sys(pi + f, vn);
-                                store_f64_sys(pcv + f, cvn);
-                            } else {
-                                store_f64_sys(pu + f, un);
-                                store_f64_sys(pcu + f, cun);
-                                pi[f] = vn;
-                                pcv[f] = cvn;
-                            }
-                            nrm += un * un + vn * vn;
-                        }
-                    }
-                    if (act && lg == 0) err2 += e * e;
-                    // ---- publish: every store of this wave has left before any of its counters moves ----
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (act && lg == 0) __hip_atomic_store(a.ver + s, sq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    if ((taken >> lane) & 1ull) ++cur;
+        for (int c = 0; c < R; ++c) {
+            const int f = p.lg + G * c;
+            if (p.act && f < a.k) {
+                double un = uf[c], cun = cu[c], vn = vf[c], cvn = cv[c];
+                pmf_row_step(wt, vf[c], un, cun, a.hy);
+                pmf_row_step(wt, un, vn, cvn, a.hy);
+                if (OWN_USER) {
+                    pu[f] = un;
+                    pcu[f] = cun;
+                    store_f64_sys(pi + f, vn);
+                    store_f64_sys(pcv + f, cvn);
+                } else {
+                    store_f64_sys(pu + f, un);
+                    store_f64_sys(pcu + f, cun);
+                    pi[f] = vn;
+                    pcv[f] = cvn;
                 }
+                nrm += un * un + vn * vn;
             }
-            if (mine) a.row_cur[q] = cur;
-            unfinished = unfinished || __ballot(mine && cur < rend) != 0ull;
         }
-        if (!unfinished) break;
-        if (progressed) {
-            t_idle = 0;
-            idle_sweeps = 0;
-            continue;
-        }
-        // nothing of this wave can run yet: back off (longer the longer it lasts) and watch the bound
-        ++idle_sweeps;
-        if (idle_sweeps < 8) __builtin_amdgcn_s_sleep(8);
-        else if (idle_sweeps < 64) __builtin_amdgcn_s_sleep(64);
-        else __builtin_amdgcn_s_sleep(127);
-        if ((idle_sweeps & 255u) == 0) {
-            const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-            if (t_idle == 0) t_idle = now;
-            int bad = 0;
-            if (lane == 0 && (now - t_idle > (unsigned long long)a.wait_bound_ticks ||
-                              __hip_atomic_load(a.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM))) {
-                if (atomicCAS(a.abort, 0u, 1u) == 0u) a.abort[1] = (unsigned int)w;
-                bad = 1;
-            }
-            give_up = __builtin_amdgcn_readfirstlane(bad) != 0;
-        }
-    }
+        if (p.act && p.lg == 0) err2 += e * e;
+    });
     const double l = wave_sum_f64(err2 + a.hy.reg * nrm);
-    if (lane == 0 && l != 0.0) atomicAdd(a.loss_acc, l);
+    if (lane_id() == 0 && l != 0.0) atomicAdd(a.loss_acc, l);
 }
 
 }  // namespace chip
@@ -409,30 +291,11 @@ static void pmf_epoch_levels(cornac_hip_mf_t h, const PmfHyper &hy, int variant,
 
 // as mf_epoch_chain: false when the runtime refuses the cooperative launch (nothing has run)
 static bool pmf_epoch_chain(cornac_hip_mf_t h, int G, const PmfHyper &hy, int variant, double *loss_slot) {
-    HIP_CHECK(hipMemsetAsync(h->uver.p, 0, h->uver.n * sizeof(unsigned int), h->stream));
-    HIP_CHECK(hipMemsetAsync(h->chain_abort.p, 0, 8 * sizeof(unsigned int), h->stream));
-    HIP_CHECK(hipMemcpyAsync(h->c_row_cur.p, h->c_row_beg.p, h->c_row_beg.n * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
     PmfChainArgs a;
-    a.wrow_ptr = h->c_wrow_ptr.p; a.row_id = h->c_row_id.p; a.row_end = h->c_row_end.p; a.row_cur = h->c_row_cur.p;
-    a.csid = h->c_sid.p; a.cseq = h->c_seq.p; a.cr = h->c_r.p;
-    a.ver = h->uver.p; a.abort = h->chain_abort.p;
+    a.c = chain_args(h->chain, h->c_sid.p, h->c_seq.p, h->c_r.p);
     a.U = h->pmf_U.p; a.V = h->pmf_V.p; a.CU = h->pmf_cu.p; a.CV = h->pmf_cv.p; a.loss_acc = loss_slot;
     a.k = h->k; a.hy = hy;
-    a.wait_bound_ticks = (long long)prof_env_int("CORNAC_HIP_MF_CHAIN_WAIT_S", 120) * 100000000ll;
-    void *kargs[] = {(void *)&a};
-    const hipError_t st = hipLaunchCooperativeKernel((const void *)pick_pmf_chain_kernel(h->k, G, h->chain_own_user, variant),
-                                                     dim3(h->chain_grid), dim3(kBlock), kargs, 0, h->stream);
-    if (st == hipErrorCooperativeLaunchTooLarge) {
-        (void)hipGetLastError();
-        return false;
-    }
-    HIP_CHECK(st);
-    unsigned int ab[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(ab, h->chain_abort.p, sizeof ab, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (ab[0])
-        fail(CORNAC_HIP_ERR_HIP, "PMF dataflow kernel: wave %u made no progress for its time bound (internal error)", ab[1]);
-    return true;
+    return chain_launch(h->stream, h->chain, pick_pmf_chain_kernel(h->k, G, h->chain_own_user, variant), &a, "PMF dataflow kernel");
 }
 
 extern "C" {
@@ -481,7 +344,7 @@ int cornac_hip_mf_pmf_fit(cornac_hip_mf_t h, int n_epochs, float lr, float reg, 
             // plan an MF fit of the handle has already sized beyond that is not used
             const int per_cu = pmf_chain_per_cu(h, G);
             mf_build_chain(h, per_cu);
-            chain = h->chain_grid <= device_info(h->device).cus * std::max(1, std::min(per_cu, 8) / 2);
+            chain = h->chain.grid <= device_info(h->device).cus * std::max(1, std::min(per_cu, 8) / 2);
         }
         for (int e = 0; e < n_epochs; ++e) {
             if (chain && pmf_epoch_chain(h, G, hy, variant, h->pmf_loss.p + e)) {

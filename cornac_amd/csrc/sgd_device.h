@@ -52,6 +52,13 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
     return (r0 + r1) + (r2 + r3);
 }
 
+// butterfly sum of a double over the wave (loss terms: compared with a tolerance)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+    return v;
+}
+
 // acc = ((acc + p[0]) + p[1]) + ... + p[lim-1] over the lanes of a G-lane group, in lane order (the reference's
 // sequential float sum over factors).  With one group per wave every term is read with v_readlane (constant
 // lane after unrolling); smaller groups need a per-group source lane and go through the cross-lane network.

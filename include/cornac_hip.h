@@ -440,6 +440,11 @@ int cornac_hip_mf_get_factors(cornac_hip_mf_t h, float *U, float *V, float *Bu, 
  * epochs_run receives the number of epochs executed. */
 int cornac_hip_mf_fit(cornac_hip_mf_t h, int max_iter, float lr, float reg, float mu, int use_bias, int early_stop,
                       int mode, float *loss_per_epoch, int *epochs_run);
+/* Form of the last deterministic epoch of cornac_hip_mf_fit: *form = 1 the persistent dataflow launch (k <= 256 and
+ * nnz >= 4096), 2 one launch per level of the row-conflict schedule (also after a refused cooperative launch), 0 none
+ * yet; *own_user = 1 if the dataflow launch's waves owned the user rows, 0 if the item rows (0 unless *form is 1).
+ * Either pointer may be NULL. */
+int cornac_hip_mf_det_form(cornac_hip_mf_t h, int *form, int *own_user);
 /* Form of the hogwild MF epoch: 0 = automatic, 1 = the fused kernel (user rows owned by waves, item rows by fp32
  * atomics), 2 = the block rotation (csrc/mf_blocks.inc: item bins in the CUs' LDS, user blocks rotating among the 32
  * workgroups of an XCD, 8 launches x 32 barrier-separated sub-rounds per epoch; no atomics, every update applied exactly
