@@ -81,6 +81,11 @@ SYMBOLS = [
     "cornac_hip_vaecf_create", "cornac_hip_vaecf_destroy", "cornac_hip_vaecf_set_params", "cornac_hip_vaecf_get_params",
     "cornac_hip_vaecf_get_state", "cornac_hip_vaecf_reset_optimizer", "cornac_hip_vaecf_fit_epoch",
     "cornac_hip_vaecf_encode_users", "cornac_hip_vaecf_score_users", "cornac_hip_vaecf_score_pairs",
+    "cornac_hip_bivae_create", "cornac_hip_bivae_destroy", "cornac_hip_bivae_set_params", "cornac_hip_bivae_get_params",
+    "cornac_hip_bivae_set_factors", "cornac_hip_bivae_get_factors", "cornac_hip_bivae_get_state",
+    "cornac_hip_bivae_reset_optimizer", "cornac_hip_bivae_fit_epoch", "cornac_hip_bivae_last_timing",
+    "cornac_hip_bivae_infer_means",
+    "cornac_hip_bivae_score_users", "cornac_hip_bivae_score_pairs",
 ]
 
 
@@ -329,6 +334,21 @@ def lib():
         L.cornac_hip_vaecf_encode_users.argtypes = [_vp, _vp, C.c_int64, _vp]
         L.cornac_hip_vaecf_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
         L.cornac_hip_vaecf_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_bivae_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                              C.c_int]
+        L.cornac_hip_bivae_destroy.argtypes = [_vp]
+        L.cornac_hip_bivae_set_params.argtypes = [_vp, _vp]
+        L.cornac_hip_bivae_get_params.argtypes = [_vp, _vp]
+        L.cornac_hip_bivae_set_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
+        L.cornac_hip_bivae_get_factors.argtypes = [_vp, _vp, _vp, _vp, _vp]
+        L.cornac_hip_bivae_get_state.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.cornac_hip_bivae_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_bivae_fit_epoch.argtypes = [_vp, C.c_int64, C.c_float, C.c_float, _vp, _vp, C.c_uint64, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), _vp]
+        L.cornac_hip_bivae_last_timing.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.cornac_hip_bivae_infer_means.argtypes = [_vp]
+        L.cornac_hip_bivae_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_bivae_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
         _lib = L
     return _lib
 
@@ -1401,3 +1421,119 @@ class VaecfModel(_HandleOwner):
 
     def score_pairs(self, users, items):
         return _score_by_ids("cornac_hip_vaecf_score_pairs", self.h_, np.float32, users, items)
+
+
+BIVAE_RANGE = 512   # CORNAC_HIP_BIVAE_RANGE: rows of the other side's table per workgroup of the fused decode's dense pass
+
+
+class BivaeModel(_HandleOwner):
+    """Owner of a cornac_hip_bivae_t handle: the binarised training matrix in both orientations, the 12 tables of the
+    reference's BiVAE (cornac/models/bivaecf/bivae.py:66-86) with Adam's moments and the two step counters, the factor tables
+    theta, beta, mu_theta, mu_beta (bivae.py:48-53), the epoch of bivae.py:194-256, the final passes of :258-274 and the
+    scores of recom_bivaecf.py:217-224.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
+    _DESTROY = "cornac_hip_bivae_destroy"
+    _HANDLE = "h_"   # (`h` is the hidden size here)
+    NAMES = ("user_encoder.fc0.weight", "user_encoder.fc0.bias", "user_mu.weight", "user_mu.bias", "user_std.weight",
+             "user_std.bias", "item_encoder.fc0.weight", "item_encoder.fc0.bias", "item_mu.weight", "item_mu.bias",
+             "item_std.weight", "item_std.bias")
+    FACTORS = ("theta", "beta", "mu_theta", "mu_beta")
+    ACTS = ("tanh", "sigmoid", "relu", "relu6", "elu")
+    LIKELIHOODS = ("bern", "gaus", "pois")
+    RANGE = BIVAE_RANGE
+
+    @staticmethod
+    def shapes(n_users, n_items, k, h):
+        side = lambda n: ((h, n), (h,), (k, h), (k,), (k, h), (k,))   # noqa: E731
+        return dict(zip(BivaeModel.NAMES, side(n_items) + side(n_users)))
+
+    @staticmethod
+    def factor_shapes(n_users, n_items, k):
+        return dict(zip(BivaeModel.FACTORS, ((n_users, k), (n_items, k), (n_users, k), (n_items, k))))
+
+    def __init__(self, X, k, h, act_fn="tanh", likelihood="pois", device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.k, self.h = int(k), int(h)
+        indptr, indices, _ = _csr_arrays(X)
+        self.h_ = _vp()
+        check(lib().cornac_hip_bivae_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
+                                            self.k, self.h, self.ACTS.index(act_fn), self.LIKELIHOODS.index(likelihood)))
+
+    def _empty(self):
+        sh = self.shapes(self.n_users, self.n_items, self.k, self.h)
+        return {n: np.empty(sh[n], np.float32) for n in self.NAMES}
+
+    def _pointers(self, tables):
+        return (_vp * 12)(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.NAMES])
+
+    def set_params(self, params):
+        sh = self.shapes(self.n_users, self.n_items, self.k, self.h)
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
+        check(lib().cornac_hip_bivae_set_params(self.h_, self._pointers(tables)))
+
+    def get_params(self):
+        out = self._empty()
+        check(lib().cornac_hip_bivae_get_params(self.h_, self._pointers(out)))
+        return out
+
+    def set_factors(self, theta=None, beta=None, mu_theta=None, mu_beta=None):
+        sh = self.factor_shapes(self.n_users, self.n_items, self.k)
+        tabs = [_f32c(a) for a in (theta, beta, mu_theta, mu_beta)]
+        for n, a in zip(self.FACTORS, tabs):
+            assert a is None or a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
+        check(lib().cornac_hip_bivae_set_factors(self.h_, *[_ptr(a) for a in tabs]))
+
+    def get_factors(self):
+        """{theta, beta, mu_theta, mu_beta}"""
+        sh = self.factor_shapes(self.n_users, self.n_items, self.k)
+        out = {n: np.empty(sh[n], np.float32) for n in self.FACTORS}
+        check(lib().cornac_hip_bivae_get_factors(self.h_, *[_ptr(out[n]) for n in self.FACTORS]))
+        return out
+
+    def get_state(self):
+        """(m, v, t_user, t_item): Adam's exp_avg and exp_avg_sq per table, and the two optimisers' step counters"""
+        m, v, tu, ti = self._empty(), self._empty(), C.c_int64(), C.c_int64()
+        check(lib().cornac_hip_bivae_get_state(self.h_, self._pointers(m), self._pointers(v), C.byref(tu), C.byref(ti)))
+        return m, v, int(tu.value), int(ti.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_bivae_reset_optimizer(self.h_))
+
+    def n_steps(self, batch_size):
+        """(item steps, user steps) of an epoch"""
+        bs = max(int(batch_size), 1)
+        return -(-self.n_items // bs), -(-self.n_users // bs)
+
+    def fit_epoch(self, batch_size, lr, beta_kl, eps_item=None, eps_user=None, seed=0):
+        """one epoch: the item steps, then the user steps.  eps_item [2, n_items, k] and eps_user [2, n_users, k] are the noise
+        of the training forward (plane 0) and of the forward after the step (plane 1); None: the device generator under
+        `seed`.  Returns (the sum of the item steps' batch-mean losses, that of the user steps, the per-step losses, item
+        steps first)."""
+        eps = []
+        for e, n in ((eps_item, self.n_items), (eps_user, self.n_users)):
+            if e is not None:
+                e = np.ascontiguousarray(e, np.float32)
+                assert e.shape == (2, n, self.k)
+            eps.append(e)
+        steps = np.zeros(sum(self.n_steps(batch_size)), np.float64)
+        li, lu = C.c_double(), C.c_double()
+        check(lib().cornac_hip_bivae_fit_epoch(self.h_, int(batch_size), float(lr), float(beta_kl), _ptr(eps[0]), _ptr(eps[1]),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(li), C.byref(lu), _ptr(steps)))
+        return float(li.value), float(lu.value), steps
+
+    def last_timing(self):
+        """(item pass, user pass) of the last fit_epoch in seconds of device time"""
+        ti, tu = C.c_double(), C.c_double()
+        check(lib().cornac_hip_bivae_last_timing(self.h_, C.byref(ti), C.byref(tu)))
+        return ti.value * 1e-3, tu.value * 1e-3
+
+    def infer_means(self):
+        check(lib().cornac_hip_bivae_infer_means(self.h_))
+
+    def score_users(self, users):
+        """sigmoid(mu_theta[u] . mu_beta^T): [n, n_items] float32"""
+        return _score_by_ids("cornac_hip_bivae_score_users", self.h_, np.float32, users, width=self.n_items)
+
+    def score_pairs(self, users, items):
+        return _score_by_ids("cornac_hip_bivae_score_pairs", self.h_, np.float32, users, items)

@@ -23,49 +23,21 @@
 // LDS): f32-input MFMA has vector FMA's peak on this part, and the chains keep a fixed ascending order this way.
 #include "sparse_model.h"
 #include "rng.h"
+#include "vae_device.h"
 
 namespace chip {
 namespace {
 
-constexpr int kVaeBlock = 256;
 constexpr int kVaeMaxK = 256, kVaeMaxH = 1024, kVaeMaxBatch = 1024;
 constexpr int kVaeTile = 64, kVaeTk = 16;
 constexpr float kVaeEps = 1e-10f;
 constexpr int64_t kVaeScoreBytes = 256ll << 20;   // a scoring chunk's logits (at most kVaeMaxBatch users)
-enum { ACT_TANH = 0, ACT_SIGMOID, ACT_RELU, ACT_RELU6, ACT_ELU, ACT_COUNT };
 enum { LIK_MULT = 0, LIK_BERN, LIK_GAUS, LIK_POIS, LIK_COUNT };
 
 // offsets (floats) of the ten tables in the parameter buffer; m and v use the same layout
 struct VaeLayout {
     int64_t W1, b1, Wm, bm, Wv, bv, D0, c0, D1, c1, total;
 };
-
-struct VaeAdam {
-    float omb1, b2, omb2, step, bc2s, eps;
-};
-
-__device__ inline void vae_adam(float *w, float *m, float *v, int64_t idx, float g, const VaeAdam &a) {
-    float mm = m[idx];
-    mm = mm + (g - mm) * a.omb1;
-    const float vv = v[idx] * a.b2 + a.omb2 * g * g;
-    m[idx] = mm;
-    v[idx] = vv;
-    const float denom = sqrtf(vv) / a.bc2s + a.eps;
-    w[idx] = w[idx] - a.step * (mm / denom);
-}
-
-__device__ inline float vae_act(int act, float x, float *d) {
-    switch (act) {
-    case ACT_TANH: { const float t = tanhf(x); *d = 1.f - t * t; return t; }
-    case ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-x)); *d = s * (1.f - s); return s; }
-    case ACT_RELU: *d = x > 0.f ? 1.f : 0.f; return x > 0.f ? x : 0.f;
-    case ACT_RELU6: *d = (x > 0.f && x < 6.f) ? 1.f : 0.f; return fminf(fmaxf(x, 0.f), 6.f);
-    default:
-        if (x > 0.f) { *d = 1.f; return x; }
-        *d = expf(x);
-        return expm1f(x);
-    }
-}
 
 // fixed tree over the workgroup's 256 values
 __device__ inline float vae_block_sum(float v, float *sh) {

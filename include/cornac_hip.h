@@ -855,6 +855,69 @@ int cornac_hip_vaecf_encode_users(cornac_hip_vaecf_t h, const int32_t *users, in
 int cornac_hip_vaecf_score_users(cornac_hip_vaecf_t h, const int32_t *users, int64_t n, float *out);
 int cornac_hip_vaecf_score_pairs(cornac_hip_vaecf_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
 
+/* ------------------------------------------------------------------------- *
+ * BiVAECF (Truong, Salah, Lauw 2021, "Bilateral VAE"), float32 throughout, one hidden layer per encoder, standard normal
+ * priors (no CAP priors).
+ * Replaces: BiVAE.forward / BiVAE.loss / learn, cornac/models/bivaecf/bivae.py:34-276, and BiVAECF.score,
+ *           cornac/models/bivaecf/recom_bivaecf.py:193-225.
+ * The handle owns the binarised training CSR (sorted indices without repeats, checked; stored values are never read:
+ * every stored entry counts as 1, as bivae.py:190 does), its CSC, the 12 tables with Adam's m and v, one Adam step counter
+ * per side, and the four factor tables theta [U x k], beta [I x k], mu_theta [U x k], mu_beta [I x k] (bivae.py:48-53),
+ * all of which persist across calls.  Tables are passed as arrays of 12 pointers in the order and with the shapes of the
+ * reference's state_dict:
+ *   0 user_encoder.fc0.weight [h x I]   1 user_encoder.fc0.bias [h]   2 user_mu.weight [k x h]    3 user_mu.bias [k]
+ *   4 user_std.weight [k x h]           5 user_std.bias [k]
+ *   6 item_encoder.fc0.weight [h x U]   7 item_encoder.fc0.bias [h]   8 item_mu.weight [k x h]    9 item_mu.bias [k]
+ *  10 item_std.weight [k x h]          11 item_std.bias [k]
+ * (the device keeps tables 0 and 6 transposed).  A NULL entry skips its table.
+ * act: 0 tanh, 1 sigmoid, 2 relu, 3 relu6, 4 elu (alpha 1).  likelihood: 0 bern, 1 gaus, 2 pois.
+ * Supported: 1 <= k <= 256, 1 <= h <= 1024, 1 <= batch_size <= 1024; anything else is CORNAC_HIP_ERR_INVALID with a
+ * message naming the limit.  No float atomics; every sum has one fixed order: the same inputs give the same bits.
+ * The decoder's B x N probabilities (bivae.py:111-117) are never stored: a fused pass over fixed ranges of
+ * CORNAC_HIP_BIVAE_RANGE rows of the other side's table gives each batch row's log-likelihood and gradient.
+ * ------------------------------------------------------------------------- */
+#define CORNAC_HIP_BIVAE_RANGE 512
+typedef struct cornac_hip_bivae *cornac_hip_bivae_t;
+
+/* bivae.py:35-86 (the model's shape) and :189-191 (X and its transpose, here never densified); all tables start as zeros */
+int cornac_hip_bivae_create(cornac_hip_bivae_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                            const int32_t *indices, int k, int h, int act, int likelihood);
+int cornac_hip_bivae_destroy(cornac_hip_bivae_t h);
+/* the 12 tables from / to the host (state_dict of bivae.py:66-86) */
+int cornac_hip_bivae_set_params(cornac_hip_bivae_t h, const float *const *tables);
+int cornac_hip_bivae_get_params(cornac_hip_bivae_t h, float *const *tables);
+/* theta, beta, mu_theta, mu_beta (bivae.py:48-53) from / to the host; NULL skips */
+int cornac_hip_bivae_set_factors(cornac_hip_bivae_t h, const float *theta, const float *beta, const float *mu_theta,
+                                 const float *mu_beta);
+int cornac_hip_bivae_get_factors(cornac_hip_bivae_t h, float *theta, float *beta, float *mu_theta, float *mu_beta);
+/* Adam's exp_avg (m) and exp_avg_sq (v), in the tables' shapes, and the step counters of u_optimizer and i_optimizer
+ * (bivae.py:186-187); NULL skips */
+int cornac_hip_bivae_get_state(cornac_hip_bivae_t h, float *const *m, float *const *v, int64_t *t_user, int64_t *t_item);
+/* m = v = 0, both counters 0: what the two new torch.optim.Adam of bivae.py:186-187 (once per learn()) start from */
+int cornac_hip_bivae_reset_optimizer(cornac_hip_bivae_t h);
+/* One epoch of bivae.py:194-256: ceil(n_items / batch_size) item steps, then ceil(n_users / batch_size) user steps, over
+ * consecutive id ranges (item_iter / user_iter without shuffling).  A step is a forward against the other side's whole
+ * sampled table as it stands (a constant), the backward, torch.optim.Adam's dense sweep (betas 0.9 / 0.999, eps 1e-8)
+ * over the side's six tables, and a second forward with the updated tables whose sample and mean go to the side's rows
+ * of beta / mu_beta or theta / mu_theta (bivae.py:220-223, 250-252).  All of it is enqueued from this one call with one
+ * synchronise at the end.  eps_item [2 x n_items x k], eps_user [2 x n_users x k]: plane 0 is the noise of the training
+ * forward's reparameterize() (bivae.py:119-121), plane 1 that of the forward after the step, row = id; NULL draws on the
+ * device (Philox keyed by seed, side, step, draw, row, factor).  loss_item / loss_user: the sum over the side's steps of
+ * the batch-mean loss (i_sum_loss / u_sum_loss of bivae.py:217, 247); step_loss [item steps + user steps]: each of them,
+ * item steps first.  Any may be NULL. */
+int cornac_hip_bivae_fit_epoch(cornac_hip_bivae_t h, int64_t batch_size, float lr, float beta_kl, const float *eps_item,
+                               const float *eps_user, uint64_t seed, double *loss_item, double *loss_user, double *step_loss);
+/* device time (stream events) of the last fit_epoch's item pass and user pass, noise upload or generation included, in
+ * milliseconds; either may be NULL */
+int cornac_hip_bivae_last_timing(cornac_hip_bivae_t h, double *item_ms, double *user_ms);
+/* bivae.py:258-274: mu_beta and mu_theta again from the tables as they stand */
+int cornac_hip_bivae_infer_means(cornac_hip_bivae_t h);
+/* out [n x n_items] = sigmoid(mu_theta[u] . mu_beta^T) (recom_bivaecf.py:217-220); score_pairs: out[p] is the entry
+ * items[p] of users[p]'s row (recom_bivaecf.py:221-224, before its scaling), the bits of the matching score_users entry.
+ * An id out of range is named in the error. */
+int cornac_hip_bivae_score_users(cornac_hip_bivae_t h, const int32_t *users, int64_t n, float *out);
+int cornac_hip_bivae_score_pairs(cornac_hip_bivae_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif
