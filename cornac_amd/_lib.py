@@ -86,6 +86,9 @@ SYMBOLS = [
     "cornac_hip_bivae_reset_optimizer", "cornac_hip_bivae_fit_epoch", "cornac_hip_bivae_last_timing",
     "cornac_hip_bivae_infer_means",
     "cornac_hip_bivae_score_users", "cornac_hip_bivae_score_pairs",
+    "cornac_hip_ncf_create", "cornac_hip_ncf_destroy", "cornac_hip_ncf_n_tables", "cornac_hip_ncf_set_params",
+    "cornac_hip_ncf_get_params", "cornac_hip_ncf_get_state", "cornac_hip_ncf_reset_optimizer", "cornac_hip_ncf_fit_epoch",
+    "cornac_hip_ncf_draw_epoch", "cornac_hip_ncf_fit_epoch_sampled", "cornac_hip_ncf_score_users", "cornac_hip_ncf_score_pairs",
 ]
 
 
@@ -349,6 +352,20 @@ def lib():
         L.cornac_hip_bivae_infer_means.argtypes = [_vp]
         L.cornac_hip_bivae_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
         L.cornac_hip_bivae_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_ncf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, _vp, C.c_int,
+                                            C.c_int]
+        L.cornac_hip_ncf_destroy.argtypes = [_vp]
+        L.cornac_hip_ncf_n_tables.argtypes = [_vp, C.POINTER(C.c_int)]
+        L.cornac_hip_ncf_set_params.argtypes = [_vp, _vp]
+        L.cornac_hip_ncf_get_params.argtypes = [_vp, _vp]
+        L.cornac_hip_ncf_get_state.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_ncf_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_ncf_fit_epoch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_double), _vp]
+        L.cornac_hip_ncf_draw_epoch.argtypes = [_vp, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]
+        L.cornac_hip_ncf_fit_epoch_sampled.argtypes = [_vp, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int,
+                                                       C.POINTER(C.c_double), _vp]
+        L.cornac_hip_ncf_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_ncf_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
         _lib = L
     return _lib
 
@@ -1537,3 +1554,129 @@ class BivaeModel(_HandleOwner):
 
     def score_pairs(self, users, items):
         return _score_by_ids("cornac_hip_bivae_score_pairs", self.h_, np.float32, users, items)
+
+
+class NcfModel(_HandleOwner):
+    """Owner of a cornac_hip_ncf_t handle: the training CSR with its values, the tables of the reference's GMF / MLP / NeuMF
+    module (cornac/models/ncf/backend_pt.py:22-175) with the learner's state and step counter, the epoch of
+    recom_ncf_base.py:266-281 over given or device-drawn samples, and the scores of the three _score_pt.  Tables travel as
+    dicts keyed by the reference's state_dict names, in its shapes."""
+    _DESTROY = "cornac_hip_ncf_destroy"
+    KINDS = ("GMF", "MLP", "NeuMF")
+    ACTS = ("sigmoid", "tanh", "elu", "selu", "relu", "relu6", "leaky_relu")
+    LEARNERS = ("adam", "sgd", "rmsprop", "adagrad")
+    MAX_STEP = 16384   # samples of one step: batch_size * (1 + num_neg)
+
+    @staticmethod
+    def NAMES(kind, layers=()):
+        gmf = ("user_embedding.weight", "item_embedding.weight", "logit.weight", "logit.bias")
+        mlp = ("user_embedding.weight", "item_embedding.weight") + tuple(
+            "mlp_model.%d.%s" % (2 * l, p) for l in range(max(len(layers) - 1, 0)) for p in ("weight", "bias")) + ("logit.weight", "logit.bias")
+        if kind == "GMF":
+            return gmf
+        if kind == "MLP":
+            return mlp
+        return ("logit.weight", "logit.bias") + tuple("gmf." + n for n in gmf) + tuple("mlp." + n for n in mlp)
+
+    @staticmethod
+    def UNUSED(kind):
+        """the tables that forward() does not use: no gradient, no update"""
+        return ("gmf.logit.weight", "gmf.logit.bias", "mlp.logit.weight", "mlp.logit.bias") if kind == "NeuMF" else ()
+
+    @staticmethod
+    def shapes(kind, n_users, n_items, num_factors=0, layers=()):
+        f, layers = int(num_factors), tuple(int(x) for x in layers)
+        gmf = ((n_users, f), (n_items, f), (1, f), (1,))
+        mlp = ()
+        if kind != "GMF":
+            mlp = ((n_users, layers[0] // 2), (n_items, layers[0] // 2))
+            for l in range(len(layers) - 1):
+                mlp += ((layers[l + 1], layers[l]), (layers[l + 1],))
+            mlp += ((1, layers[-1]), (1,))
+        sh = gmf if kind == "GMF" else mlp if kind == "MLP" else ((1, f + layers[-1]), (1,)) + gmf + mlp
+        return dict(zip(NcfModel.NAMES(kind, layers), sh))
+
+    def __init__(self, kind, X, num_factors=8, layers=(64, 32, 16, 8), act_fn="relu", device=0):
+        self.kind = kind
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.num_factors = 0 if kind == "MLP" else int(num_factors)
+        self.layers = () if kind == "GMF" else tuple(int(x) for x in layers)
+        self.names = self.NAMES(kind, self.layers)
+        self._shapes = self.shapes(kind, self.n_users, self.n_items, self.num_factors, self.layers)
+        indptr, indices, data = _csr_arrays(X)
+        self.nnz = int(indptr[-1])
+        lay = np.ascontiguousarray(self.layers, np.int32)
+        self.h = _vp()
+        check(lib().cornac_hip_ncf_create(C.byref(self.h), device, self.KINDS.index(kind), self.n_users, self.n_items, _ptr(indptr),
+                                          _ptr(indices), _ptr(data), self.num_factors, _ptr(lay) if len(lay) else None, len(lay),
+                                          0 if kind == "GMF" else self.ACTS.index(act_fn)))
+        n = C.c_int()
+        check(lib().cornac_hip_ncf_n_tables(self.h, C.byref(n)))
+        assert n.value == len(self.names)
+
+    def _empty(self):
+        return {n: np.empty(self._shapes[n], np.float32) for n in self.names}
+
+    def _pointers(self, tables):
+        return (_vp * len(self.names))(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.names])
+
+    def set_params(self, params):
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == self._shapes[n], "%s is %r, not %r" % (n, a.shape, self._shapes[n])
+        check(lib().cornac_hip_ncf_set_params(self.h, self._pointers(tables)))
+
+    def get_params(self):
+        out = self._empty()
+        check(lib().cornac_hip_ncf_get_params(self.h, self._pointers(out)))
+        return out
+
+    def get_state(self):
+        """(s1, s2, t): adam's exp_avg and exp_avg_sq, rmsprop's square_avg or adagrad's sum in s1, and the step counter"""
+        s1, s2, t = self._empty(), self._empty(), C.c_int64()
+        check(lib().cornac_hip_ncf_get_state(self.h, self._pointers(s1), self._pointers(s2), C.byref(t)))
+        return s1, s2, int(t.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_ncf_reset_optimizer(self.h))
+
+    def fit_epoch(self, step_ptr, users, items, labels, lr, reg=0.0, learner="adam"):
+        """one epoch over the given samples, step s being [step_ptr[s], step_ptr[s + 1]).  Returns (the sum of the steps' mean
+        losses, the per-step losses)."""
+        step_ptr = np.ascontiguousarray(step_ptr, np.int64)
+        users, items = np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32)
+        labels = np.ascontiguousarray(labels, np.float32)
+        assert len(step_ptr) >= 2 and len(users) == len(items) == len(labels) == int(step_ptr[-1])
+        steps = np.zeros(len(step_ptr) - 1, np.float64)
+        total = C.c_double()
+        check(lib().cornac_hip_ncf_fit_epoch(self.h, len(steps), _ptr(step_ptr), _ptr(users), _ptr(items), _ptr(labels), float(lr),
+                                             float(reg), self.LEARNERS.index(learner), C.byref(total), _ptr(steps)))
+        return float(total.value), steps
+
+    def n_steps(self, batch_size):
+        return -(-self.nnz // max(int(batch_size), 1))
+
+    def draw_epoch(self, batch_size, num_neg, seed=0, epoch=0):
+        """(step_ptr, users, items, labels) of the device sampler's epoch, without training"""
+        total = self.nnz * (1 + max(int(num_neg), 0))
+        step_ptr = np.zeros(self.n_steps(batch_size) + 1, np.int64)
+        users, items, labels = np.empty(total, np.int32), np.empty(total, np.int32), np.empty(total, np.float32)
+        check(lib().cornac_hip_ncf_draw_epoch(self.h, int(batch_size), int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              int(epoch) & 0xFFFFFFFFFFFFFFFF, _ptr(step_ptr), _ptr(users), _ptr(items), _ptr(labels)))
+        return step_ptr, users, items, labels
+
+    def fit_epoch_sampled(self, batch_size, num_neg, lr, reg=0.0, learner="adam", seed=0, epoch=0):
+        """one epoch over exactly draw_epoch's samples, drawn on the device.  Returns as fit_epoch does."""
+        steps = np.zeros(max(self.n_steps(batch_size), 1), np.float64)
+        total = C.c_double()
+        check(lib().cornac_hip_ncf_fit_epoch_sampled(self.h, int(batch_size), int(num_neg), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                     int(epoch) & 0xFFFFFFFFFFFFFFFF, float(lr), float(reg),
+                                                     self.LEARNERS.index(learner), C.byref(total), _ptr(steps)))
+        return float(total.value), steps
+
+    def score_users(self, users):
+        """forward(u, every item): [n, n_items] float32 probabilities"""
+        return _score_by_ids("cornac_hip_ncf_score_users", self.h, np.float32, users, width=self.n_items)
+
+    def score_pairs(self, users, items):
+        return _score_by_ids("cornac_hip_ncf_score_pairs", self.h, np.float32, users, items)

@@ -127,32 +127,9 @@ __host__ __device__ __forceinline__ uint32_t ldsbin_rot(uint32_t g, uint32_t key
     return h % n_bins;
 }
 
-__host__ __device__ __forceinline__ uint32_t ldsbin_mix(uint32_t h) {
-    h ^= h >> 15; h *= 0x85EBCA77u;
-    h ^= h >> 13; h *= 0xC2B2AE3Du;
-    h ^= h >> 16;
-    return h;
-}
-
-// keyed bijection of [0, n): an alternating unbalanced Feistel network (3 double rounds) on the next power of two,
-// cycle-walked back into range (< 2 walks on average)
-__host__ __device__ inline uint32_t ldsbin_perm(uint32_t x, uint32_t n, uint32_t key) {
-    if (n <= 1u) return 0u;
-    int bits = 32 - __builtin_clz(n - 1u);
-    if (bits < 2) bits = 2;
-    const int lb = bits >> 1, rb = bits - lb;
-    const uint32_t lm = (1u << lb) - 1u, rm = (1u << rb) - 1u;
-    do {
-        uint32_t l = x >> rb, r = x & rm;
-#pragma unroll
-        for (uint32_t round = 0; round < 3u; ++round) {
-            l ^= (ldsbin_mix(r * 0x9E3779B1u + key + round * 0x7F4A7C15u) >> 7) & lm;
-            r ^= (ldsbin_mix(l * 0x85EBCA6Bu + (key ^ 0x5BD1E995u) + round * 0x165667B1u) >> 7) & rm;
-        }
-        x = (l << rb) | r;
-    } while (x >= n);
-    return x;
-}
+// the mixer and the keyed bijection of [0, n) live in rng.h (mix32, feistel_perm)
+__host__ __device__ __forceinline__ uint32_t ldsbin_mix(uint32_t h) { return mix32(h); }
+__host__ __device__ __forceinline__ uint32_t ldsbin_perm(uint32_t x, uint32_t n, uint32_t key) { return feistel_perm(x, n, key); }
 
 // The deal.  n_groups = ceil(n_items / n_bins) groups of n_bins positions; stratum s of n_strata covers the groups
 // [s n_groups / n_strata, (s + 1) n_groups / n_strata) and the ranks of their positions (the last one ends at n_items).

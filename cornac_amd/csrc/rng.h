@@ -42,6 +42,35 @@ __host__ __device__ inline uint32_t lemire_bounded2(uint32_t wa, uint32_t wb, ui
 }
 __host__ __device__ inline uint32_t lemire_thresh(uint32_t n) { return (uint32_t)(0u - n) % n; }
 
+// ---------------------------------------------------------------- keyed bijection ----------------
+// (moved here from bpr_ldsbin.inc as they stood: the LDS-bin deal and NCF's epoch order of the stored entries use them)
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t h) {
+    h ^= h >> 15; h *= 0x85EBCA77u;
+    h ^= h >> 13; h *= 0xC2B2AE3Du;
+    h ^= h >> 16;
+    return h;
+}
+
+// keyed bijection of [0, n): an alternating unbalanced Feistel network (3 double rounds) on the next power of two,
+// cycle-walked back into range (< 2 walks on average)
+__host__ __device__ inline uint32_t feistel_perm(uint32_t x, uint32_t n, uint32_t key) {
+    if (n <= 1u) return 0u;
+    int bits = 32 - __builtin_clz(n - 1u);
+    if (bits < 2) bits = 2;
+    const int lb = bits >> 1, rb = bits - lb;
+    const uint32_t lm = (1u << lb) - 1u, rm = (1u << rb) - 1u;
+    do {
+        uint32_t l = x >> rb, r = x & rm;
+#pragma unroll
+        for (uint32_t round = 0; round < 3u; ++round) {
+            l ^= (mix32(r * 0x9E3779B1u + key + round * 0x7F4A7C15u) >> 7) & lm;
+            r ^= (mix32(l * 0x85EBCA6Bu + (key ^ 0x5BD1E995u) + round * 0x165667B1u) >> 7) & rm;
+        }
+        x = (l << rb) | r;
+    } while (x >= n);
+    return x;
+}
+
 // ---------------------------------------------------------------- MT19937 -----------------------
 struct MtStreamParams {
     uint32_t *state;   // [624] device, persistent generator state

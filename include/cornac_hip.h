@@ -918,6 +918,66 @@ int cornac_hip_bivae_infer_means(cornac_hip_bivae_t h);
 int cornac_hip_bivae_score_users(cornac_hip_bivae_t h, const int32_t *users, int64_t n, float *out);
 int cornac_hip_bivae_score_pairs(cornac_hip_bivae_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Neural collaborative filtering (He et al. 2017): GMF, MLP and NeuMF, float32 throughout, the PyTorch backend's semantics.
+ * Replaces: GMF / MLP / NeuMF .forward, cornac/models/ncf/backend_pt.py:22-175; the batch loop of _fit_pt,
+ *           cornac/models/ncf/recom_ncf_base.py:240-293 (one step: :266-281); the sampler it calls,
+ *           Dataset.uir_iter(num_zeros=), cornac/data/dataset.py:445-488; and _score_pt,
+ *           cornac/models/ncf/recom_gmf.py:162-173, recom_mlp.py:172-183, recom_neumf.py:277-291.
+ * One handle holds the training CSR with its values, the model's tables in the reference's state_dict order and shapes
+ *   GMF    user_embedding.weight [U x F], item_embedding.weight [I x F], logit.weight [1 x F], logit.bias [1]
+ *   MLP    user_embedding.weight [U x L0/2], item_embedding.weight [I x L0/2], mlp_model.{0,2,..}.weight [L(l+1) x L(l)] and
+ *          .bias, logit.weight [1 x L(-1)], logit.bias
+ *   NeuMF  logit.weight [1 x (F + L(-1))], logit.bias, gmf.<GMF's four>, mlp.<MLP's>
+ * two state arrays per table for the learner, and one step counter.  NeuMF's gmf.logit.* and mlp.logit.* take no part in
+ * forward() and have no gradient: no learner touches them or their state (torch skips parameters whose grad is None).
+ * Limits, each a named refusal: 1 <= num_factors <= 256; 2 <= n_layers <= 8; layers[0] even in 2 .. 512; every other width
+ * in 1 .. 256; 1 <= samples of a step <= 16384; NeuMF needs layers[n_layers - 1] == num_factors (backend_pt.py:139).
+ * No float atomics; every sum has one fixed order; the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct cornac_hip_ncf *cornac_hip_ncf_t;
+enum { CORNAC_HIP_NCF_GMF = 0, CORNAC_HIP_NCF_MLP = 1, CORNAC_HIP_NCF_NEUMF = 2 };
+enum { CORNAC_HIP_NCF_ADAM = 0, CORNAC_HIP_NCF_SGD = 1, CORNAC_HIP_NCF_RMSPROP = 2, CORNAC_HIP_NCF_ADAGRAD = 3 };
+
+/* backend_pt.py:22-37, 61-85, 122-147.  indptr / indices / data: the training CSR with sorted indices and finite values (the
+ * sampler's `dok_matrix[u, j] > 0`).  num_factors is ignored for MLP, layers / act for GMF.  act: 0 sigmoid, 1 tanh, 2 elu,
+ * 3 selu, 4 relu, 5 relu6, 6 leaky_relu (slope 0.01), backend_pt.py:11-19.  All tables start as zeros. */
+int cornac_hip_ncf_create(cornac_hip_ncf_t *out, int device, int kind, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                          const int32_t *indices, const double *data, int num_factors, const int *layers, int n_layers, int act);
+int cornac_hip_ncf_destroy(cornac_hip_ncf_t h);
+/* the number of tables: 4 (GMF), 4 + 2 (n_layers - 1) (MLP), their sum + 2 (NeuMF) */
+int cornac_hip_ncf_n_tables(cornac_hip_ncf_t h, int *n);
+/* the tables from / to the host, in state_dict order; a NULL entry is skipped */
+int cornac_hip_ncf_set_params(cornac_hip_ncf_t h, const float *const *tables);
+int cornac_hip_ncf_get_params(cornac_hip_ncf_t h, float *const *tables);
+/* the learner's state in the tables' shapes and its step counter: adam s1 = exp_avg, s2 = exp_avg_sq; rmsprop s1 = square_avg;
+ * adagrad s1 = sum; otherwise zeros.  NULL skips. */
+int cornac_hip_ncf_get_state(cornac_hip_ncf_t h, float *const *s1, float *const *s2, int64_t *t);
+/* state = 0, t = 0: what the new optimiser of recom_ncf_base.py:255-259 (once per fit) starts from */
+int cornac_hip_ncf_reset_optimizer(cornac_hip_ncf_t h);
+/* One epoch of recom_ncf_base.py:266-281 over the given samples: step s is the samples [step_ptr[s], step_ptr[s + 1]) of
+ * users / items / labels (labels in [0, 1]).  A step: forward, nn.BCELoss (mean; logs clamped at -100), the backward as
+ * torch computes it (dL/dp = (p - y) / max(p (1 - p), 1e-12) / n), and the learner's DENSE update of every entry of every
+ * table that has a gradient, with g += reg * p first (torch's weight_decay): adam (betas 0.9 / 0.999, eps 1e-8), sgd,
+ * rmsprop (alpha 0.99, eps 1e-8), adagrad (eps 1e-10).  The samples are uploaded once and all steps are enqueued from this
+ * call, with one synchronise at the end.  loss_sum: the sum of the steps' mean losses; step_loss [steps]: each. */
+int cornac_hip_ncf_fit_epoch(cornac_hip_ncf_t h, int64_t steps, const int64_t *step_ptr, const int32_t *users, const int32_t *items,
+                             const float *labels, float lr, float reg, int learner, double *loss_sum, double *step_loss);
+/* The device sampler's epoch (dataset.py:445-488 in distribution, not draw for draw): the stored entries once each in an order
+ * permuted under (seed, epoch), label 1, in steps of batch_size; each step is [positives | negatives, user-major], every
+ * positive followed by num_neg items uniform among those j for which (u, j) is not stored with a value > 0, label 0.
+ * step_ptr [ceil(nnz / batch_size) + 1]; users, items, labels [nnz * (1 + num_neg)].  Refused by name when num_neg > 0 and
+ * some user rates every item positively. */
+int cornac_hip_ncf_draw_epoch(cornac_hip_ncf_t h, int64_t batch_size, int num_neg, uint64_t seed, uint64_t epoch, int64_t *step_ptr,
+                              int32_t *users, int32_t *items, float *labels);
+/* fit_epoch over exactly draw_epoch's samples, which never leave the device; step_loss [ceil(nnz / batch_size)] */
+int cornac_hip_ncf_fit_epoch_sampled(cornac_hip_ncf_t h, int64_t batch_size, int num_neg, uint64_t seed, uint64_t epoch, float lr,
+                                     float reg, int learner, double *loss_sum, double *step_loss);
+/* out [n x n_items] = forward(u, every item); score_pairs: out[p] = forward(users[p], items[p]), the bits of the matching
+ * score_users entry.  An id out of range is named in the error. */
+int cornac_hip_ncf_score_users(cornac_hip_ncf_t h, const int32_t *users, int64_t n, float *out);
+int cornac_hip_ncf_score_pairs(cornac_hip_ncf_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif
