@@ -206,12 +206,14 @@ static void mf_fit_minibatch_impl(cornac_hip_mf_t h, const int64_t *order, int64
             ++h->opt_step;
             MbOpt o;
             o.kind = optimizer; o.lr = lr; o.wd = reg;
-            o.beta1 = 0.9f; o.beta2 = 0.999f; o.one_minus_beta1 = 1.f - o.beta1; o.one_minus_beta2 = 1.f - o.beta2;
+            // torch holds the betas and alpha as doubles and rounds 1 - beta to float32 when the tensor operation takes it:
+            // 1.f - 0.999f is 1.3e-5 below (float)(1.0 - 0.999), which put every early Adam step 6.4e-6 off
+            o.beta1 = 0.9f; o.beta2 = 0.999f; o.one_minus_beta1 = (float)(1.0 - 0.9); o.one_minus_beta2 = (float)(1.0 - 0.999);
             const double bc1 = 1.0 - std::pow(0.9, (double)h->opt_step), bc2 = 1.0 - std::pow(0.999, (double)h->opt_step);
             o.step_size = (float)((double)lr / bc1);
             o.bc2_sqrt = (float)std::sqrt(bc2);
             o.eps = optimizer == CORNAC_HIP_OPT_ADAGRAD ? 1e-10f : 1e-8f;
-            o.alpha = 0.99f; o.one_minus_alpha = 1.f - o.alpha;
+            o.alpha = 0.99f; o.one_minus_alpha = (float)(1.0 - 0.99);
             const int grad_grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 15) / 16, 4096));
             mf_mb_grad_kernel<<<grad_grid, 256, 0, s>>>(h->opt_order.p + b0, n, h->rid.p, h->cid.p, h->val.p, t, k, mu,
                                                        use_bias, h->loss.p, d_ku ? d_ku + (size_t)b0 * k : nullptr,
