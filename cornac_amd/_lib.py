@@ -89,6 +89,9 @@ SYMBOLS = [
     "cornac_hip_ncf_create", "cornac_hip_ncf_destroy", "cornac_hip_ncf_n_tables", "cornac_hip_ncf_set_params",
     "cornac_hip_ncf_get_params", "cornac_hip_ncf_get_state", "cornac_hip_ncf_reset_optimizer", "cornac_hip_ncf_fit_epoch",
     "cornac_hip_ncf_draw_epoch", "cornac_hip_ncf_fit_epoch_sampled", "cornac_hip_ncf_score_users", "cornac_hip_ncf_score_pairs",
+    "cornac_hip_lightgcn_create", "cornac_hip_lightgcn_destroy", "cornac_hip_lightgcn_set_params", "cornac_hip_lightgcn_get_params",
+    "cornac_hip_lightgcn_get_state", "cornac_hip_lightgcn_reset_optimizer", "cornac_hip_lightgcn_fit_epoch",
+    "cornac_hip_lightgcn_propagate",
 ]
 
 
@@ -366,6 +369,14 @@ def lib():
                                                        C.POINTER(C.c_double), _vp]
         L.cornac_hip_ncf_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
         L.cornac_hip_ncf_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_lightgcn_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int]
+        L.cornac_hip_lightgcn_destroy.argtypes = [_vp]
+        L.cornac_hip_lightgcn_set_params.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_lightgcn_get_params.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_lightgcn_get_state.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_lightgcn_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_lightgcn_fit_epoch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]
+        L.cornac_hip_lightgcn_propagate.argtypes = [_vp, _vp, _vp]
         _lib = L
     return _lib
 
@@ -1680,3 +1691,62 @@ class NcfModel(_HandleOwner):
 
     def score_pairs(self, users, items):
         return _score_by_ids("cornac_hip_ncf_score_pairs", self.h, np.float32, users, items)
+
+
+class LightGcnModel(_HandleOwner):
+    """Owner of a cornac_hip_lightgcn_t handle: the normalised adjacency of the train matrix's bipartite graph
+    (cornac/models/lightgcn/lightgcn.py:13-41), the layer-0 tables `feature_dict.user` / `feature_dict.item` with Adam's state
+    and step counter, the epoch of recom_lightgcn.py:157-179 over given triplets, and the final embeddings of model(graph)."""
+    _DESTROY = "cornac_hip_lightgcn_destroy"
+    PIECE = 512        # edges of one piece of a long row: rows above it are summed in pieces, combined in piece order
+    MAX_STEP = 16384   # triplets of one step
+    NAMES = ("user", "item")
+
+    def __init__(self, X, emb_size=64, num_layers=3, device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.emb_size, self.num_layers = int(emb_size), int(num_layers)
+        indptr, indices, _ = _csr_arrays(X)
+        self.nnz = int(indptr[-1])
+        self.h = _vp()
+        check(lib().cornac_hip_lightgcn_create(C.byref(self.h), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
+                                               self.emb_size, self.num_layers))
+
+    def _empty(self):
+        return np.empty((self.n_users, self.emb_size), np.float32), np.empty((self.n_items, self.emb_size), np.float32)
+
+    def set_params(self, user=None, item=None):
+        user, item = _f32c(user), _f32c(item)
+        assert user is None or user.shape == (self.n_users, self.emb_size), "user is %r" % (user.shape,)
+        assert item is None or item.shape == (self.n_items, self.emb_size), "item is %r" % (item.shape,)
+        check(lib().cornac_hip_lightgcn_set_params(self.h, _ptr(user), _ptr(item)))
+
+    def get_params(self):
+        user, item = self._empty()
+        check(lib().cornac_hip_lightgcn_get_params(self.h, _ptr(user), _ptr(item)))
+        return user, item
+
+    def get_state(self):
+        """(m_user, m_item, v_user, v_item, t): Adam's exp_avg and exp_avg_sq and its step counter"""
+        (mu, mi), (vu, vi), t = self._empty(), self._empty(), C.c_int64()
+        check(lib().cornac_hip_lightgcn_get_state(self.h, _ptr(mu), _ptr(mi), _ptr(vu), _ptr(vi), C.byref(t)))
+        return mu, mi, vu, vi, int(t.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_lightgcn_reset_optimizer(self.h))
+
+    def fit_epoch(self, step_ptr, users, pos, neg, lr, lambda_reg):
+        """one epoch over the given triplets, step s being [step_ptr[s], step_ptr[s + 1]).  Returns the per-step (losses, bpr,
+        reg): bpr + lambda_reg * reg, mean softplus, the halved squared norms over the batch size."""
+        step_ptr = np.ascontiguousarray(step_ptr, np.int64)
+        users, pos, neg = (np.ascontiguousarray(a, np.int32) for a in (users, pos, neg))
+        assert len(step_ptr) >= 2 and len(users) == len(pos) == len(neg) == int(step_ptr[-1])
+        losses, bpr, reg = (np.zeros(len(step_ptr) - 1, np.float64) for _ in range(3))
+        check(lib().cornac_hip_lightgcn_fit_epoch(self.h, len(losses), _ptr(step_ptr), _ptr(users), _ptr(pos), _ptr(neg), float(lr),
+                                                  float(lambda_reg), _ptr(losses), _ptr(bpr), _ptr(reg)))
+        return losses, bpr, reg
+
+    def propagate(self):
+        """(U, V): the final embeddings, the mean of the layers' tables"""
+        user, item = self._empty()
+        check(lib().cornac_hip_lightgcn_propagate(self.h, _ptr(user), _ptr(item)))
+        return user, item

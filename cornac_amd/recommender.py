@@ -218,6 +218,32 @@ class Recommender(_RecommenderRoot):
         self._drop_scorer()
         return self
 
+    def monitor_value(self, train_set, val_set):
+        """the value `early_stop` watches, larger being better (recommender.py:582-599); None: nothing to watch, never stop"""
+        return None
+
+    def early_stop(self, train_set, val_set, min_delta=0.0, patience=0):
+        """True when training should stop: the monitored value has not risen by `min_delta` for `patience` epochs in a row
+        (recommender.py:601-651, over the fields of `reset_info`)"""
+        self.current_epoch += 1
+        current_value = self.monitor_value(train_set, val_set)
+        if current_value is None:
+            return False
+        if np.greater_equal(current_value - self.best_value, min_delta):
+            self.best_value = current_value
+            self.best_epoch = self.current_epoch
+            self.wait = 0
+        else:
+            self.wait += 1
+            if self.wait >= patience:
+                self.stopped_epoch = self.current_epoch
+        if self.stopped_epoch > 0:
+            print("Early stopping:")
+            print("- best epoch = {}, stopped epoch = {}".format(self.best_epoch, self.stopped_epoch))
+            print("- best monitored value = {:.6f} (delta = {:.6f})".format(self.best_value, current_value - self.best_value))
+            return True
+        return False
+
     def transform(self, test_set):
         """hook called by the evaluation method before scoring a test set (recommender.py:410-421); nothing to cache here"""
 

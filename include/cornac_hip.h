@@ -978,6 +978,50 @@ int cornac_hip_ncf_fit_epoch_sampled(cornac_hip_ncf_t h, int64_t batch_size, int
 int cornac_hip_ncf_score_users(cornac_hip_ncf_t h, const int32_t *users, int64_t n, float *out);
 int cornac_hip_ncf_score_pairs(cornac_hip_ncf_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * LightGCN (He et al. 2020): graph propagation, the BPR step and Adam, float32 throughout.
+ * Replaces: construct_graph and its edge norms, cornac/models/lightgcn/lightgcn.py:13-41; GCNLayer.forward and
+ *           Model.forward over the whole graph, lightgcn.py:44-117 (DGL's multi_update_all, once per layer, forward and
+ *           backward); Model.loss_fn, lightgcn.py:119-134; the batch loop of LightGCN.fit with torch.optim.Adam,
+ *           cornac/models/lightgcn/recom_lightgcn.py:143-181 (one step: :168-179); the eval-mode model(graph) of :185-189.
+ * One handle holds the normalised adjacency of the bipartite graph as one CSR over the n_users + n_items nodes (the train
+ * matrix's rows, then its transpose's, with one float32 weight per edge, (deg_u deg_i)^-1/2 as lightgcn.py:31-39 computes it),
+ * the layer-0 tables E0_user [n_users x emb_size] and E0_item [n_items x emb_size], Adam's exp_avg and exp_avg_sq and its
+ * step counter.  Nodes without edges are legal.  The final embeddings are E = P(E0), P = 1 / (L + 1) sum_k A^k; P is linear
+ * and symmetric, so the gradient of the layer-0 tables is P(G) for the gradient G at the final embeddings: one kernel both
+ * ways, no activations kept.
+ * Limits, each a named refusal: 1 <= emb_size <= 256; 0 <= num_layers <= 8; 1 <= triplets of a step <= 16384; sorted
+ * indices without repeats; nnz < 2^31; n_users + n_items < 2^31.
+ * No atomics; every sum has one fixed order (a row's edges ascending, rows longer than 512 edges in pieces combined in
+ * piece order, a node's gradient rows in sample order); the same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct cornac_hip_lightgcn *cornac_hip_lightgcn_t;
+
+/* lightgcn.py:13-41, 64-82.  indptr / indices: the train matrix as a CSR over n_users x n_items (total_users x total_items:
+ * rows and columns without entries are nodes without edges).  All tables start as zeros. */
+int cornac_hip_lightgcn_create(cornac_hip_lightgcn_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                               const int32_t *indices, int emb_size, int num_layers);
+int cornac_hip_lightgcn_destroy(cornac_hip_lightgcn_t h);
+/* the layer-0 tables (feature_dict.user, feature_dict.item) from / to the host; NULL skips */
+int cornac_hip_lightgcn_set_params(cornac_hip_lightgcn_t h, const float *user, const float *item);
+int cornac_hip_lightgcn_get_params(cornac_hip_lightgcn_t h, float *user, float *item);
+/* Adam's exp_avg (m) and exp_avg_sq (v) in the tables' shapes and its step counter; NULL skips */
+int cornac_hip_lightgcn_get_state(cornac_hip_lightgcn_t h, float *m_user, float *m_item, float *v_user, float *v_item, int64_t *t);
+/* state = 0, t = 0: the new torch.optim.Adam of recom_lightgcn.py:143 */
+int cornac_hip_lightgcn_reset_optimizer(cornac_hip_lightgcn_t h);
+/* One epoch of recom_lightgcn.py:157-179 over the given triplets: step s is [step_ptr[s], step_ptr[s + 1]) of users / pos /
+ * neg.  A step of B triplets: E = P(E0); x = <a, n> - <a, p> over the rows a = E_user[u], p = E_item[i], n = E_item[j];
+ * bpr = mean softplus(x) (linear above 20), reg = (|a|^2 + |p|^2 + |n|^2) / 2 / B, loss = bpr + lambda_reg reg; the gradient
+ * rows (s (n - p) + lambda a) / B, (-s a + lambda p) / B, (s a + lambda n) / B with s = sigmoid(x), summed per node in sample
+ * order (an item's positives before its negatives); g = P(G); torch's Adam over every entry of both tables (betas 0.9 /
+ * 0.999, eps 1e-8, no weight decay).  The triplets are uploaded once and all steps are enqueued from this call, with one
+ * synchronise at the end.  loss_out / bpr_out / reg_out [steps]: each step's three losses; NULL skips. */
+int cornac_hip_lightgcn_fit_epoch(cornac_hip_lightgcn_t h, int64_t steps, const int64_t *step_ptr, const int32_t *users,
+                                  const int32_t *pos, const int32_t *neg, float lr, float lambda_reg, double *loss_out,
+                                  double *bpr_out, double *reg_out);
+/* the final embeddings E = P(E0): model(graph) in eval mode, lightgcn.py:92-117 with users = None; NULL skips */
+int cornac_hip_lightgcn_propagate(cornac_hip_lightgcn_t h, float *user_out, float *item_out);
+
 #ifdef __cplusplus
 }
 #endif
