@@ -92,6 +92,8 @@ SYMBOLS = [
     "cornac_hip_lightgcn_create", "cornac_hip_lightgcn_destroy", "cornac_hip_lightgcn_set_params", "cornac_hip_lightgcn_get_params",
     "cornac_hip_lightgcn_get_state", "cornac_hip_lightgcn_reset_optimizer", "cornac_hip_lightgcn_fit_epoch",
     "cornac_hip_lightgcn_propagate",
+    "cornac_hip_ngcf_create", "cornac_hip_ngcf_destroy", "cornac_hip_ngcf_set_params", "cornac_hip_ngcf_get_params",
+    "cornac_hip_ngcf_get_state", "cornac_hip_ngcf_reset_optimizer", "cornac_hip_ngcf_fit_epoch", "cornac_hip_ngcf_propagate",
 ]
 
 
@@ -377,6 +379,14 @@ def lib():
         L.cornac_hip_lightgcn_reset_optimizer.argtypes = [_vp]
         L.cornac_hip_lightgcn_fit_epoch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]
         L.cornac_hip_lightgcn_propagate.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_ngcf_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_uint64]
+        L.cornac_hip_ngcf_destroy.argtypes = [_vp]
+        L.cornac_hip_ngcf_set_params.argtypes = [_vp, _vp, _vp, _vp]
+        L.cornac_hip_ngcf_get_params.argtypes = [_vp, _vp, _vp, _vp]
+        L.cornac_hip_ngcf_get_state.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64)]
+        L.cornac_hip_ngcf_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_ngcf_fit_epoch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]
+        L.cornac_hip_ngcf_propagate.argtypes = [_vp, _vp, _vp]
         _lib = L
     return _lib
 
@@ -1749,4 +1759,95 @@ class LightGcnModel(_HandleOwner):
         """(U, V): the final embeddings, the mean of the layers' tables"""
         user, item = self._empty()
         check(lib().cornac_hip_lightgcn_propagate(self.h, _ptr(user), _ptr(item)))
+        return user, item
+
+
+class NgcfModel(_HandleOwner):
+    """Owner of a cornac_hip_ngcf_t handle: the graph of cornac/models/ngcf/ngcf.py:14-37 with its edge norms, the tables
+    `feature_dict.user` / `feature_dict.item` and every layer's W1 / W2 with Adam's state and step counter, the train-mode epoch
+    of recom_ngcf.py:159-184 over given triplets, and the concatenated embeddings of the eval-mode model(graph).  Parameters
+    travel as dicts under the reference's state_dict names, in its order (`names`)."""
+    _DESTROY = "cornac_hip_ngcf_destroy"
+    PIECE = 512          # edges of one piece of a long row (the hop is LightGCN's)
+    MAX_STEP = 16384     # triplets of one step
+    WGRAD_ROWS = 2048    # rows of one chunk of the weight and bias gradients; the chunks' partials are added in chunk order
+
+    @staticmethod
+    def param_shapes(n_users, n_items, emb_size, layer_sizes):
+        """name -> shape, in the reference's state_dict order: the layers' Linears, then feature_dict.item, feature_dict.user"""
+        from collections import OrderedDict
+
+        out, din = OrderedDict(), int(emb_size)
+        for l, dout in enumerate(int(x) for x in layer_sizes):
+            for w in ("W1", "W2"):
+                out["layers.%d.%s.weight" % (l, w)] = (dout, din)
+                out["layers.%d.%s.bias" % (l, w)] = (dout,)
+            din = dout
+        out["feature_dict.item"] = (int(n_items), int(emb_size))
+        out["feature_dict.user"] = (int(n_users), int(emb_size))
+        return out
+
+    def __init__(self, X, emb_size=64, layer_sizes=(64, 64, 64), dropout_rates=(0.1, 0.1, 0.1), dropout_key=0, device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.emb_size = int(emb_size)
+        self.layer_sizes, self.dropout_rates = [int(x) for x in layer_sizes], [float(x) for x in dropout_rates]
+        assert len(self.layer_sizes) == len(self.dropout_rates), "'layer_sizes' and 'dropout_rates' must be of the same size"
+        self.dropout_key = int(dropout_key) & 0xFFFFFFFFFFFFFFFF
+        self.D = self.emb_size + sum(self.layer_sizes)
+        self.shapes = self.param_shapes(self.n_users, self.n_items, self.emb_size, self.layer_sizes)
+        self.names = list(self.shapes)
+        indptr, indices, _ = _csr_arrays(X)
+        self.nnz = int(indptr[-1])
+        sizes, rates = np.asarray(self.layer_sizes, np.int32), np.asarray(self.dropout_rates, np.float32)
+        self.h = _vp()
+        check(lib().cornac_hip_ngcf_create(C.byref(self.h), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
+                                           self.emb_size, len(sizes), _ptr(sizes), _ptr(rates), self.dropout_key))
+
+    def _empty(self):
+        from collections import OrderedDict
+
+        return OrderedDict((n, np.empty(s, np.float32)) for n, s in self.shapes.items())
+
+    def _args(self, tables):
+        """(user, item, layers[4 L]) pointers of a dict of tables; a missing name skips"""
+        at = lambda n: None if tables.get(n) is None else tables[n].ctypes.data   # noqa: E731
+        layers = (_vp * (4 * len(self.layer_sizes)))(*[at("layers.%d.%s" % (l, s)) for l in range(len(self.layer_sizes))
+                                                       for s in ("W1.weight", "W1.bias", "W2.weight", "W2.bias")])
+        return at("feature_dict.user"), at("feature_dict.item"), layers
+
+    def set_params(self, params):
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == self.shapes[n], "%s is %r, not %r" % (n, a.shape, self.shapes[n])
+        check(lib().cornac_hip_ngcf_set_params(self.h, *self._args(tables)))
+
+    def get_params(self):
+        out = self._empty()
+        check(lib().cornac_hip_ngcf_get_params(self.h, *self._args(out)))
+        return out
+
+    def get_state(self):
+        """(m, v, t): Adam's exp_avg and exp_avg_sq as dicts like get_params', and its step counter"""
+        m, v, t = self._empty(), self._empty(), C.c_int64()
+        check(lib().cornac_hip_ngcf_get_state(self.h, *(self._args(m) + self._args(v) + (C.byref(t),))))
+        return m, v, int(t.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_ngcf_reset_optimizer(self.h))
+
+    def fit_epoch(self, step_ptr, users, pos, neg, lr, lambda_reg):
+        """one train-mode epoch over the given triplets, step s being [step_ptr[s], step_ptr[s + 1]).  Returns the per-step
+        (losses, bpr, reg) as LightGcnModel.fit_epoch does."""
+        step_ptr = np.ascontiguousarray(step_ptr, np.int64)
+        users, pos, neg = (np.ascontiguousarray(a, np.int32) for a in (users, pos, neg))
+        assert len(step_ptr) >= 2 and len(users) == len(pos) == len(neg) == int(step_ptr[-1])
+        losses, bpr, reg = (np.zeros(len(step_ptr) - 1, np.float64) for _ in range(3))
+        check(lib().cornac_hip_ngcf_fit_epoch(self.h, len(losses), _ptr(step_ptr), _ptr(users), _ptr(pos), _ptr(neg), float(lr),
+                                              float(lambda_reg), _ptr(losses), _ptr(bpr), _ptr(reg)))
+        return losses, bpr, reg
+
+    def propagate(self):
+        """(U [n_users x D], V [n_items x D]): the concatenated embeddings in eval mode (no dropout)"""
+        user, item = np.empty((self.n_users, self.D), np.float32), np.empty((self.n_items, self.D), np.float32)
+        check(lib().cornac_hip_ngcf_propagate(self.h, _ptr(user), _ptr(item)))
         return user, item

@@ -40,7 +40,63 @@ def _initial_tables(n_users, n_items, emb_size):
     return user.numpy().astype(np.float32).copy(), item.numpy().astype(np.float32).copy()
 
 
-class LightGCN(Recommender):
+class GraphRecommender(Recommender):
+    """What the two graph models (LightGCN, NGCF) share on the host: the train matrix over all nodes, the monitored value of
+    early stopping, and scoring from the learned embeddings `U` and `V` through the fused scorer with zero bases."""
+
+    def _graph_matrix(self, train_set):
+        """the train matrix over total_users x total_items (lightgcn.py:22-30), sorted indices"""
+        u, i, _ = train_set.uir_tuple
+        X = sp.csr_matrix((np.ones(len(u), np.float64), (np.asarray(u, np.int64), np.asarray(i, np.int64))),
+                          shape=(self.total_users, self.total_items))
+        X.sum_duplicates()
+        X.sort_indices()
+        return X
+
+    def monitor_value(self, train_set, val_set):
+        """Recall@20 on the validation set (recom_lightgcn.py:196-227; section 4.1.2 of the paper); None without one"""
+        if val_set is None:
+            return None
+        from .eval import ranking_eval
+        from .metrics import Recall
+
+        return ranking_eval(model=self, metrics=[Recall(k=20)], train_set=train_set, test_set=val_set)[0][0]
+
+    # ---- prediction ---------------------------------------------------------------------------------
+    def _scoring_tables(self):
+        """(U, V, zeros, zeros): the score is the dot product of the final embeddings"""
+        key = (id(self.U), id(self.V))
+        cached = self.__dict__.get("_zero_bases")
+        if cached is None or cached[0] != key:
+            cached = (key, np.zeros(len(self.V), np.float32), np.zeros(len(self.U), np.float32))
+            self._zero_bases = cached
+        return self.U, self.V, cached[1], cached[2]
+
+    def _scorer_row_count(self):
+        return len(self.U)
+
+    def score(self, user_idx, item_idx=None):
+        """recom_lightgcn.py:229-260"""
+        if item_idx is None:
+            if not self.knows_user(user_idx):
+                raise ScoreException("Can't make score prediction for (user_id=%d)" % user_idx)
+            return self._get_scorer().score_user(user_idx)
+        if not (self.knows_user(user_idx) and self.knows_item(item_idx)):
+            raise ScoreException("Can't make score prediction for (user_id=%d, item_id=%d)" % (user_idx, item_idx))
+        return self.V[item_idx, :].dot(self.U[user_idx, :])
+
+    # ANN mixin surface (recom_lightgcn.py:262-290)
+    def get_vector_measure(self):
+        return "dot"
+
+    def get_user_vectors(self):
+        return self.U
+
+    def get_item_vectors(self):
+        return self.V
+
+
+class LightGCN(GraphRecommender):
     """Parameters are the reference's (recom_lightgcn.py:27-100): `emb_size`, `num_epochs`, `learning_rate`, `batch_size`,
     `num_layers`, `early_stopping` ({min_delta, patience} on Recall@20 of the validation set), `lambda_reg`, `seed`; plus
     `device`, the HIP device ordinal."""
@@ -59,15 +115,6 @@ class LightGCN(Recommender):
         self.device = device
 
     # ---- fit ----------------------------------------------------------------------------------------
-    def _graph_matrix(self, train_set):
-        """the train matrix over total_users x total_items (lightgcn.py:22-30), sorted indices"""
-        u, i, _ = train_set.uir_tuple
-        X = sp.csr_matrix((np.ones(len(u), np.float64), (np.asarray(u, np.int64), np.asarray(i, np.int64))),
-                          shape=(self.total_users, self.total_items))
-        X.sum_duplicates()
-        X.sort_indices()
-        return X
-
     def fit(self, train_set, val_set=None):
         """recom_lightgcn.py:102-194: every fit starts from new tables and a new optimiser, as there"""
         Recommender.fit(self, train_set, val_set)
@@ -110,15 +157,6 @@ class LightGCN(Recommender):
         self.U, self.V = model.propagate()
         self._drop_scorer()
 
-    def monitor_value(self, train_set, val_set):
-        """Recall@20 on the validation set (recom_lightgcn.py:196-227; section 4.1.2 of the paper); None without one"""
-        if val_set is None:
-            return None
-        from .eval import ranking_eval
-        from .metrics import Recall
-
-        return ranking_eval(model=self, metrics=[Recall(k=20)], train_set=train_set, test_set=val_set)[0][0]
-
     # ---- the tables ---------------------------------------------------------------------------------
     def state_dict(self):
         """the layer-0 tables under the reference's names (copies): they load into the reference's Model"""
@@ -156,36 +194,3 @@ class LightGCN(Recommender):
             finally:
                 model.close()
         self._drop_scorer()
-
-    # ---- prediction ---------------------------------------------------------------------------------
-    def _scoring_tables(self):
-        """(U, V, zeros, zeros): the score is the dot product of the final embeddings"""
-        key = (id(self.U), id(self.V))
-        cached = self.__dict__.get("_zero_bases")
-        if cached is None or cached[0] != key:
-            cached = (key, np.zeros(len(self.V), np.float32), np.zeros(len(self.U), np.float32))
-            self._zero_bases = cached
-        return self.U, self.V, cached[1], cached[2]
-
-    def _scorer_row_count(self):
-        return len(self.U)
-
-    def score(self, user_idx, item_idx=None):
-        """recom_lightgcn.py:229-260"""
-        if item_idx is None:
-            if not self.knows_user(user_idx):
-                raise ScoreException("Can't make score prediction for (user_id=%d)" % user_idx)
-            return self._get_scorer().score_user(user_idx)
-        if not (self.knows_user(user_idx) and self.knows_item(item_idx)):
-            raise ScoreException("Can't make score prediction for (user_id=%d, item_id=%d)" % (user_idx, item_idx))
-        return self.V[item_idx, :].dot(self.U[user_idx, :])
-
-    # ANN mixin surface (recom_lightgcn.py:262-290)
-    def get_vector_measure(self):
-        return "dot"
-
-    def get_user_vectors(self):
-        return self.U
-
-    def get_item_vectors(self):
-        return self.V

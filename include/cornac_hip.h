@@ -1022,6 +1022,53 @@ int cornac_hip_lightgcn_fit_epoch(cornac_hip_lightgcn_t h, int64_t steps, const 
 /* the final embeddings E = P(E0): model(graph) in eval mode, lightgcn.py:92-117 with users = None; NULL skips */
 int cornac_hip_lightgcn_propagate(cornac_hip_lightgcn_t h, float *user_out, float *item_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * NGCF (Wang et al. 2019): neural graph collaborative filtering, float32 throughout.
+ * Replaces: construct_graph, cornac/models/ngcf/ngcf.py:14-37; the edge norms, ngcf.py:110-117; NGCFLayer.forward,
+ *           ngcf.py:65-100 (two Linears per edge, DGL's multi_update_all, LeakyReLU, dropout, F.normalize) and
+ *           Model.forward over the whole graph, ngcf.py:150-168, forward and backward; Model.loss_fn, ngcf.py:170-185; the
+ *           batch loop of NGCF.fit with torch.optim.Adam, cornac/models/ngcf/recom_ngcf.py:148-187 (one step: :173-184); the
+ *           eval-mode model(graph) of recom_ngcf.py:190-194.
+ * One handle holds LightGCN's adjacency A (one CSR over users then items, float32 weights), the rows' weight sums c, the
+ * tables feature_dict.user [n_users x emb_size] and feature_dict.item [n_items x emb_size], per layer W1.weight
+ * [d_out x d_in], W1.bias [d_out], W2.weight, W2.bias, Adam's exp_avg and exp_avg_sq of each and its step counter.  The self
+ * loop and both edge types collapse to dense work per node:
+ *     s = A X;  z = (X + s) W1^T + (s * X) W2^T + b1 + c (b1 + b2);  a = dropout_p(leaky_relu(z, 0.2));
+ *     X' = a / max(|a|_2 per row, 1e-12);  E = [X_0 | X_1 | .. | X_L], width D = emb_size + sum(layer_sizes).
+ * The dropout mask is the device's own: a pure function of (dropout_key, Adam's step, layer, row, column) through
+ * Philox4x32-10, stated in csrc/ngcf.hip; a layer with p = 0 draws nothing.
+ * Limits, each a named refusal: 1 <= emb_size <= 256 and every layer size; 1 <= num_layers <= 8; 0 <= p < 1; 1 <= triplets
+ * of a step <= 16384; sorted indices without repeats; nnz < 2^31; n_users + n_items < 2^31.
+ * No atomics; every sum has one fixed order (the weight and bias gradients: chunks of 2048 rows, added in chunk order); the
+ * same inputs give the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct cornac_hip_ngcf *cornac_hip_ngcf_t;
+
+/* ngcf.py:14-37, 103-148.  indptr / indices: the train matrix as a CSR over n_users x n_items (total_users x total_items).
+ * layer_sizes / dropout_rates [num_layers].  All parameters start as zeros. */
+int cornac_hip_ngcf_create(cornac_hip_ngcf_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                           const int32_t *indices, int emb_size, int num_layers, const int32_t *layer_sizes, const float *dropout_rates,
+                           uint64_t dropout_key);
+int cornac_hip_ngcf_destroy(cornac_hip_ngcf_t h);
+/* the tables and layers [4 num_layers] = per layer W1.weight, W1.bias, W2.weight, W2.bias (ngcf.py:47-48, 141-148) from / to
+ * the host; a NULL pointer, a NULL entry and a NULL array skip */
+int cornac_hip_ngcf_set_params(cornac_hip_ngcf_t h, const float *user, const float *item, const float *const *layers);
+int cornac_hip_ngcf_get_params(cornac_hip_ngcf_t h, float *user, float *item, float *const *layers);
+/* Adam's exp_avg (m) and exp_avg_sq (v) in the parameters' shapes and its step counter; NULL skips */
+int cornac_hip_ngcf_get_state(cornac_hip_ngcf_t h, float *m_user, float *m_item, float *const *m_layers, float *v_user, float *v_item,
+                              float *const *v_layers, int64_t *t);
+/* state = 0, t = 0: the new torch.optim.Adam of recom_ngcf.py:148 */
+int cornac_hip_ngcf_reset_optimizer(cornac_hip_ngcf_t h);
+/* One epoch of recom_ngcf.py:159-184 over the given triplets, in train mode: step s is [step_ptr[s], step_ptr[s + 1]) of
+ * users / pos / neg.  The loss is LightGCN's over the rows of E (ngcf.py:170-185); the backward pass is written out in
+ * csrc/ngcf.hip; torch's Adam (betas 0.9 / 0.999, eps 1e-8) over every parameter.  The triplets are uploaded once and all
+ * steps are enqueued from this call, with one synchronise at the end.  loss_out / bpr_out / reg_out [steps]; NULL skips. */
+int cornac_hip_ngcf_fit_epoch(cornac_hip_ngcf_t h, int64_t steps, const int64_t *step_ptr, const int32_t *users, const int32_t *pos,
+                              const int32_t *neg, float lr, float lambda_reg, double *loss_out, double *bpr_out, double *reg_out);
+/* the concatenated embeddings U [n_users x D], V [n_items x D]: model(graph) in eval mode (no dropout), ngcf.py:150-168 with
+ * users = None; NULL skips */
+int cornac_hip_ngcf_propagate(cornac_hip_ngcf_t h, float *user_out, float *item_out);
+
 #ifdef __cplusplus
 }
 #endif
