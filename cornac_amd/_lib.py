@@ -94,6 +94,10 @@ SYMBOLS = [
     "cornac_hip_lightgcn_propagate",
     "cornac_hip_ngcf_create", "cornac_hip_ngcf_destroy", "cornac_hip_ngcf_set_params", "cornac_hip_ngcf_get_params",
     "cornac_hip_ngcf_get_state", "cornac_hip_ngcf_reset_optimizer", "cornac_hip_ngcf_fit_epoch", "cornac_hip_ngcf_propagate",
+    "cornac_hip_recvae_create", "cornac_hip_recvae_destroy", "cornac_hip_recvae_set_params", "cornac_hip_recvae_get_params",
+    "cornac_hip_recvae_get_state", "cornac_hip_recvae_reset_optimizer", "cornac_hip_recvae_update_prior",
+    "cornac_hip_recvae_get_prior_posterior", "cornac_hip_recvae_fit_epoch", "cornac_hip_recvae_encode_users",
+    "cornac_hip_recvae_score_users", "cornac_hip_recvae_score_pairs",
 ]
 
 
@@ -387,6 +391,19 @@ def lib():
         L.cornac_hip_ngcf_reset_optimizer.argtypes = [_vp]
         L.cornac_hip_ngcf_fit_epoch.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp]
         L.cornac_hip_ngcf_propagate.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_recvae_create.argtypes = [C.POINTER(_vp), C.c_int, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int]
+        L.cornac_hip_recvae_destroy.argtypes = [_vp]
+        L.cornac_hip_recvae_set_params.argtypes = [_vp, _vp]
+        L.cornac_hip_recvae_get_params.argtypes = [_vp, _vp]
+        L.cornac_hip_recvae_get_state.argtypes = [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.cornac_hip_recvae_reset_optimizer.argtypes = [_vp]
+        L.cornac_hip_recvae_update_prior.argtypes = [_vp]
+        L.cornac_hip_recvae_get_prior_posterior.argtypes = [_vp, _vp, _vp]
+        L.cornac_hip_recvae_fit_epoch.argtypes = [_vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                  _vp, _vp, C.c_uint64, _vp]
+        L.cornac_hip_recvae_encode_users.argtypes = [_vp, _vp, C.c_int64, _vp, _vp]
+        L.cornac_hip_recvae_score_users.argtypes = [_vp, _vp, C.c_int64, _vp]
+        L.cornac_hip_recvae_score_pairs.argtypes = [_vp, _vp, _vp, C.c_int64, _vp]
         _lib = L
     return _lib
 
@@ -1459,6 +1476,109 @@ class VaecfModel(_HandleOwner):
 
     def score_pairs(self, users, items):
         return _score_by_ids("cornac_hip_vaecf_score_pairs", self.h_, np.float32, users, items)
+
+
+class RecvaeModel(_HandleOwner):
+    """Owner of a cornac_hip_recvae_t handle: the training rows with their values, the 53 tables of the reference's VAE
+    (cornac/models/recvae/recvae.py:78-84: encoder, prior tables, old encoder, decoder) with the two Adams' moments and step
+    counters, the pass of recom_recvae.py:131-145, update_prior (recvae.py:116-117) and the scores of recom_recvae.py:241-278
+    in evaluation mode.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
+    _DESTROY = "cornac_hip_recvae_destroy"
+    _HANDLE = "h_"
+    ENCODER = tuple("%s%d.%s" % (kind, l, p) for l in range(1, 6) for kind in ("fc", "ln") for p in ("weight", "bias")) + (
+        "fc_mu.weight", "fc_mu.bias", "fc_logvar.weight", "fc_logvar.bias")
+    PRIORS = ("prior.mu_prior", "prior.logvar_prior", "prior.logvar_uniform_prior")
+    NAMES = tuple("encoder." + n for n in ENCODER) + PRIORS + tuple("prior.encoder_old." + n for n in ENCODER) + (
+        "decoder.weight", "decoder.bias")
+    TRAINABLE = tuple("encoder." + n for n in ENCODER) + ("decoder.weight", "decoder.bias")
+    MAX_HIDDEN, MAX_LATENT, MAX_BATCH = 1024, 256, 1024
+
+    @staticmethod
+    def shapes(n_items, hidden, latent):
+        h, k = int(hidden), int(latent)
+        enc = [((h, n_items if l == 1 else h), (h,), (h,), (h,)) for l in range(1, 6)]
+        enc = tuple(s for layer in enc for s in layer) + ((k, h), (k,), (k, h), (k,))
+        return dict(zip(RecvaeModel.NAMES, enc + ((1, k),) * 3 + enc + ((n_items, k), (n_items,))))
+
+    def __init__(self, X, hidden, latent, device=0):
+        self.n_users, self.n_items = (int(x) for x in X.shape)
+        self.hidden, self.latent = int(hidden), int(latent)
+        indptr, indices, data = _csr_arrays(X)
+        self.nnz = len(indices)
+        self.h_ = _vp()
+        check(lib().cornac_hip_recvae_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
+                                             _ptr(data), self.hidden, self.latent))
+
+    def _empty(self, names):
+        sh = self.shapes(self.n_items, self.hidden, self.latent)
+        return {n: np.empty(sh[n], np.float32) for n in names}
+
+    @staticmethod
+    def _pointers(tables, names):
+        return (_vp * len(names))(*[None if tables.get(n) is None else tables[n].ctypes.data for n in names])
+
+    def set_params(self, params):
+        sh = self.shapes(self.n_items, self.hidden, self.latent)
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
+        check(lib().cornac_hip_recvae_set_params(self.h_, self._pointers(tables, self.NAMES)))
+
+    def get_params(self):
+        out = self._empty(self.NAMES)
+        check(lib().cornac_hip_recvae_get_params(self.h_, self._pointers(out, self.NAMES)))
+        return out
+
+    def get_state(self):
+        """(m, v, t_enc, t_dec): Adam's exp_avg and exp_avg_sq per trainable table, and the two step counters"""
+        m, v, te, td = self._empty(self.TRAINABLE), self._empty(self.TRAINABLE), C.c_int64(), C.c_int64()
+        check(lib().cornac_hip_recvae_get_state(self.h_, self._pointers(m, self.TRAINABLE), self._pointers(v, self.TRAINABLE),
+                                                C.byref(te), C.byref(td)))
+        return m, v, int(te.value), int(td.value)
+
+    def reset_optimizer(self):
+        check(lib().cornac_hip_recvae_reset_optimizer(self.h_))
+
+    def update_prior(self):
+        check(lib().cornac_hip_recvae_update_prior(self.h_))
+
+    def prior_posterior(self):
+        """the old encoder's cached (mu, logvar) of every user: [n_users, latent] float32 each"""
+        mu, lv = (np.empty((self.n_users, self.latent), np.float32) for _ in range(2))
+        check(lib().cornac_hip_recvae_get_prior_posterior(self.h_, _ptr(mu), _ptr(lv)))
+        return mu, lv
+
+    def fit_epoch(self, order, batch_size, lr, gamma, beta, dropout_rate, step_encoder, step_decoder, keep=None, eps=None, seed=0):
+        """one pass over the users in `order`; keep [nnz] uint8 is the dropout mask per stored entry, eps [n_users, latent]
+        the noise (None: the device generator under `seed`).  Returns the steps' (mll, kld, negative_elbo): [steps, 3]."""
+        order = np.ascontiguousarray(order, np.int32)
+        assert order.shape == (self.n_users,)
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.uint8)
+            assert keep.shape == (self.nnz,)
+        if eps is not None:
+            eps = np.ascontiguousarray(eps, np.float32)
+            assert eps.shape == (self.n_users, self.latent)
+        steps = np.zeros((max(1, -(-self.n_users // max(int(batch_size), 1))), 3), np.float64)
+        check(lib().cornac_hip_recvae_fit_epoch(self.h_, _ptr(order), int(batch_size), float(lr), float(gamma or 0.0), float(beta or 0.0),
+                                                float(dropout_rate), int(bool(step_encoder)), int(bool(step_decoder)), _ptr(keep),
+                                                _ptr(eps), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(steps)))
+        return steps
+
+    def encode_users(self, users, with_logvar=False):
+        """mu(x_u) without dropout: [n, latent] float32 (and logvar)"""
+        users = np.ascontiguousarray(users, np.int32)
+        mu = np.empty((len(users), self.latent), np.float32)
+        lv = np.empty((len(users), self.latent), np.float32) if with_logvar else None
+        check(lib().cornac_hip_recvae_encode_users(self.h_, _ptr(users), len(users), _ptr(mu), _ptr(lv)))
+        return (mu, lv) if with_logvar else mu
+
+    def score_users(self, users):
+        """decoder(mu(x_u)), the logits: [n, n_items] float32"""
+        return _score_by_ids("cornac_hip_recvae_score_users", self.h_, np.float32, users, width=self.n_items)
+
+    def score_pairs(self, users, items):
+        return _score_by_ids("cornac_hip_recvae_score_pairs", self.h_, np.float32, users, items)
 
 
 BIVAE_RANGE = 512   # CORNAC_HIP_BIVAE_RANGE: rows of the other side's table per workgroup of the fused decode's dense pass

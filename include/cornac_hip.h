@@ -1069,6 +1069,66 @@ int cornac_hip_ngcf_fit_epoch(cornac_hip_ngcf_t h, int64_t steps, const int64_t 
  * users = None; NULL skips */
 int cornac_hip_ngcf_propagate(cornac_hip_ngcf_t h, float *user_out, float *item_out);
 
+/* ------------------------------------------------------------------------- *
+ * RecVAE (Shenbin et al. 2020), float32 throughout.
+ * Replaces: Encoder / CompositePrior / VAE.forward / update_prior, cornac/models/recvae/recvae.py:9-117, RecVAE.run,
+ *           cornac/models/recvae/recom_recvae.py:127-146, and RecVAE.score, recom_recvae.py:241-278.
+ * The handle owns the training CSR with its real values (sorted indices without repeats, finite values, checked; a stored
+ * 0.0 contributes nothing), the rows' L2 norms and sums (recvae.py:67, 100), the tables, Adam's m and v of the 26 trainable
+ * ones and the two step counters, which persist across calls.  Tables are passed as arrays of 53 pointers in the order and
+ * with the shapes of the reference's state_dict (h = hidden_dim, k = latent_dim, I = n_items):
+ *    0 .. 23  encoder.:  fc{l}.weight [h x h] (fc1: [h x I]), fc{l}.bias [h], ln{l}.weight [h], ln{l}.bias [h] for l = 1 .. 5,
+ *             then fc_mu.weight [k x h], fc_mu.bias [k], fc_logvar.weight [k x h], fc_logvar.bias [k]
+ *   24 .. 26  prior.mu_prior, prior.logvar_prior, prior.logvar_uniform_prior [1 x k]
+ *   27 .. 50  prior.encoder_old.: as 0 .. 23
+ *   51, 52    decoder.weight [I x k], decoder.bias [I]
+ * (the device keeps the two fc1.weight tables transposed).  A NULL entry skips its table.  The moments travel as arrays
+ * of 26 pointers: the encoder's 24, then the decoder's 2.
+ * Supported: 1 <= hidden_dim <= 1024, 1 <= latent_dim <= 256, 1 <= batch_size <= 1024; anything else is
+ * CORNAC_HIP_ERR_INVALID with a message naming the limit.  No float atomics; every sum has one fixed order: the same inputs
+ * give the same bits.
+ * ------------------------------------------------------------------------- */
+typedef struct cornac_hip_recvae *cornac_hip_recvae_t;
+
+/* recvae.py:49-84 (the model's shape) and recom_recvae.py:129, 136 (the batch rows, here never densified); all tables start
+ * as zeros */
+int cornac_hip_recvae_create(cornac_hip_recvae_t *out, int device, int64_t n_users, int64_t n_items, const int64_t *indptr,
+                             const int32_t *indices, const double *values, int hidden, int latent);
+int cornac_hip_recvae_destroy(cornac_hip_recvae_t h);
+/* the 53 tables from / to the host (state_dict of recvae.py:78-84) */
+int cornac_hip_recvae_set_params(cornac_hip_recvae_t h, const float *const *tables);
+int cornac_hip_recvae_get_params(cornac_hip_recvae_t h, float *const *tables);
+/* Adam's exp_avg (m) and exp_avg_sq (v) of the 26 trainable tables and the step counters of the encoder's and the
+ * decoder's optimiser (recom_recvae.py:208-209); NULL skips */
+int cornac_hip_recvae_get_state(cornac_hip_recvae_t h, float *const *m, float *const *v, int64_t *t_enc, int64_t *t_dec);
+/* m = v = 0, both counters 0: the two new torch.optim.Adam of recom_recvae.py:208-209 */
+int cornac_hip_recvae_reset_optimizer(cornac_hip_recvae_t h);
+/* recvae.py:116-117: the old encoder <- the encoder; its posterior of every user (recvae.py:35: no dropout) is computed
+ * here once, with the kernels of the training forward, and read by the steps until the next call */
+int cornac_hip_recvae_update_prior(cornac_hip_recvae_t h);
+/* that cached posterior, mu and logvar [n_users x k] (computed first where the old tables changed); NULL skips */
+int cornac_hip_recvae_get_prior_posterior(cornac_hip_recvae_t h, float *mu_out, float *logvar_out);
+/* One pass of recom_recvae.py:131-145: ceil(n_users / batch_size) steps over consecutive slices of order [n_users] (every
+ * user once: user_iter with shuffling), each a forward (recvae.py:94-111), the backward of the tables that step and
+ * torch.optim.Adam's dense sweep (betas 0.9 / 0.999, eps 1e-8) over the encoder's tables (step_encoder), the decoder's
+ * (step_decoder) or both; gradients of tables that do not step are not computed.  All steps are enqueued from this one
+ * call with one synchronise at the end.  The KL weight is gamma * sum_i x_ui, or beta where gamma == 0 (recvae.py:99-103).
+ * keep [nnz] is the input dropout's mask, one byte per stored entry in CSR order (read where dropout_rate > 0; kept entries
+ * are scaled by 1 / (1 - dropout_rate)); eps [n_users x k] is the noise of reparameterize() itself (recvae.py:89), row =
+ * user.  Either may be NULL: the device then draws it (Philox keyed by seed, the two counters' sum at the call, and entry
+ * or user and column).  step_loss [steps x 3]: mll, kld and negative_elbo of each step (recvae.py:105-107); NULL skips. */
+int cornac_hip_recvae_fit_epoch(cornac_hip_recvae_t h, const int32_t *order, int64_t batch_size, float lr, float gamma, float beta,
+                                float dropout_rate, int step_encoder, int step_decoder, const uint8_t *keep, const float *eps,
+                                uint64_t seed, double *step_loss);
+/* mu_out, logvar_out [n x k]: the encoder's output for x_u without dropout (recvae.py:95 in evaluation mode, where z = mu):
+ * score = decoder.bias + <mu(u), decoder.weight[i]>, so (mu, decoder.weight, decoder.bias) are a factor model's ranking
+ * tables; logvar_out may be NULL */
+int cornac_hip_recvae_encode_users(cornac_hip_recvae_t h, const int32_t *users, int64_t n, float *mu_out, float *logvar_out);
+/* out [n x n_items] = decoder(mu(x_u)), the logits (recom_recvae.py:260-270 in evaluation mode); score_pairs: out[p] is the
+ * entry items[p] of users[p]'s row (recom_recvae.py:278), the bits of the matching score_users entry */
+int cornac_hip_recvae_score_users(cornac_hip_recvae_t h, const int32_t *users, int64_t n, float *out);
+int cornac_hip_recvae_score_pairs(cornac_hip_recvae_t h, const int32_t *users, const int32_t *items, int64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif
