@@ -804,6 +804,8 @@ class BprTrainer(_HandleOwner):
 
     def debug_strata(self, epoch):
         """(sptr, rec_u, rec_i, rank_item, key): the partition buckets the strata form uses in `epoch`"""
+        # (a first call without buffers builds the strata grid's ownership tables, so that this works before any launch)
+        check(lib().cornac_hip_bpr_debug_strata(self.h, int(epoch), None, None, None, None, None))
         wp = self.debug_ownership()[0]
         W = len(wp) - 1
         sptr = np.empty(8 * W + 1, np.int64)

@@ -1,4 +1,6 @@
-// XCD strata: the default throughput form of BPR._fit_sgd (cornac/models/bpr/recom_bpr.pyx:231-267) on gfx950.
+// XCD strata: the throughput form of BPR._fit_sgd (cornac/models/bpr/recom_bpr.pyx:231-267) on gfx950 for catalogues that
+// no LDS-bin plan fits — hog_form (bpr.hip) tries the LDS bins first and takes this form by itself from 2^20 items on; the
+// multi-GPU driver forces it.
 // (textually included by bpr.hip after the handle; device code lives in namespace chip)
 //
 // The reference's threads update U / V / B rows in place without any synchronisation (racy Hogwild).  On a single

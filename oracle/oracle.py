@@ -492,6 +492,81 @@ def strata_buckets(wave_ptr, own_u, own_i, deg, key, n_hot):
     return sptr, rec_u, rec_i, rank_item
 
 
+def strata_n_hot(deg, nnz, n_items, hot_permille=120, hot_min_mult_x100=200):
+    """the hot-set rule of csrc/bpr.hip build_item_ranks in the same double arithmetic: the leading popularity ranks whose
+    expected touches per epoch (degree + the uniform share nnz / n_items of the negative draws) are at least
+    hot_min_mult_x100 / 100 times the mean row's and that together stay within hot_permille / 1000 of all 2 nnz item-row
+    touches; the walk stops at the first rank that fails either condition"""
+    deg = np.asarray(deg, np.int64)
+    order = np.argsort(-deg, kind="stable")
+    neg_share = float(nnz) / float(n_items)
+    mean_touch = 2.0 * neg_share
+    cap = 2.0 * float(nnz) * int(hot_permille) / 1000.0
+    cum, n_hot = 0.0, 0
+    for r in range(int(n_items)):
+        touch = float(deg[order[r]]) + neg_share
+        if touch * 100.0 < mean_touch * int(hot_min_mult_x100) or cum + touch > cap:
+            break
+        cum += touch
+        n_hot = r + 1
+    return n_hot
+
+
+def strata_unr(k):
+    """triplets per wave step of the strata kernel the dispatcher returns for k (csrc/bpr.hip pick_strata_kernel)"""
+    return 4 if k <= 64 else 2 if k <= 192 else 1
+
+
+def _strata_triplets(seed, epoch, s_begin, n, indptr, indices, n_items, ownership, k, hot_permille, hot_min_mult_x100,
+                     rehash_period):
+    nnz = len(indices)
+    first_phase = lambda s: (8 * int(s) + nnz - 1) // nnz
+    p_lo, p_hi = first_phase(s_begin), 8 if s_begin + n >= nnz else first_phase(s_begin + n)
+    wave_ptr, own_u, own_i = ownership
+    W = len(wave_ptr) - 1
+    deg = np.bincount(indices, minlength=n_items)
+    n_hot = strata_n_hot(deg, nnz, n_items, hot_permille, hot_min_mult_x100)
+    key = strata_key(seed, int(epoch) // max(1, int(rehash_period)))
+    sptr, rec_u, rec_i, rank_item = strata_buckets(wave_ptr, own_u, own_i, deg, key, n_hot)
+    unr = strata_unr(k)
+    cols = {name: [] for name in ("su", "si", "code", "wave", "phase", "t")}
+    for ph in range(p_lo, p_hi):
+        for w in range(W):
+            p = ((w // 4) % 8 + ph) % 8
+            base, length = int(sptr[8 * w + p]), int(sptr[8 * w + p + 1] - sptr[8 * w + p])
+            if length == 0:
+                continue
+            r, code = strata_sample(seed, epoch, key, w, p, length, n_items)
+            m = len(r)  # (0 where the partition has no item: the device counts the bucket's draws as skipped)
+            assert m == length, "a partition without items: not a case for this restatement"
+            cols["su"].append(rec_u[base + r])
+            cols["si"].append(rec_i[base + r])
+            cols["code"].append(code)
+            cols["wave"].append(np.full(m, w, np.int64))
+            cols["phase"].append(np.full(m, ph, np.int64))
+            cols["t"].append(np.arange(m, dtype=np.int64))
+    cat = {name: (np.concatenate(v).astype(np.int64) if v else np.zeros(0, np.int64)) for name, v in cols.items()}
+    su, si, code = cat["su"], cat["si"], cat["code"]
+    shared = su < 0
+    u = np.where(shared, ~su, su)
+    hot_i = (si & 0x80000000) != 0
+    i = si & 0x7FFFFFFF
+    j = rank_item[code].astype(np.int64)
+    keep = ~_csr_has(indptr, indices, n_items, u, j)
+    # a tile is 64 draws; its valid draws are compacted in lane order and cut into groups of UNR
+    tile = cat["t"] // 64
+    tile_key = (cat["phase"] * W + cat["wave"]) * (1 << 20) + tile  # (ascending in the order the draws were listed)
+    assert (np.diff(tile_key) >= 0).all()
+    before = np.cumsum(keep) - keep  # valid draws before this one, over the whole list
+    first_of_tile = np.searchsorted(tile_key, tile_key, side="left")
+    pos = before - before[first_of_tile]
+    step = tile * 64 + pos // unr
+    out = dict(u=u[keep], i=i[keep], j=j[keep], skipped=int((~keep).sum()), shared=shared[keep], hot_i=hot_i[keep],
+               hot_j=(code < n_hot)[keep], wave=cat["wave"][keep], step=step[keep], phase=cat["phase"][keep],
+               n_hot=n_hot, key=key, buckets=(sptr, rec_u, rec_i, rank_item), unr=unr, phases=(p_lo, p_hi))
+    return out
+
+
 def _ldsbin_mix(h):
     """murmur3 finaliser variant of csrc/bpr_ldsbin.inc ldsbin_mix on uint32 arrays."""
     h = np.asarray(h, np.uint64) & 0xFFFFFFFF
@@ -690,7 +765,7 @@ def _csr_has(indptr, indices, n_items, u, j):
 
 def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, neg_pop=False, ownership=None, n_bins=None,
                      hot_x1000=75, share=None, strata_groups=16, hot_cost_x16=32, tables=None, deal=None, bins=None,
-                     rank_item=None):
+                     rank_item=None, k=None, hot_permille=120, hot_min_mult_x100=200, rehash_period=1):
     """The non-skipped (u, i, j) that ONE hogwild launch applies — cornac_hip_bpr_hogwild_enqueue(n) at sample offset
     s_begin of `epoch`, s_begin + n <= nnz — from the restatements of the device samplers above; integer work, exact.
 
@@ -704,14 +779,25 @@ def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, ne
                      launch order (block B of bins_per_block bins: (B bpb, (B + 1) bpb)).  The deal's key comes from `deal`,
                      the draws' from (seed, epoch); no item is hot; a launch is the whole epoch of its bins (s_begin = 0,
                      n = nnz); rank_item replaces the tables' popularity order (conveyor_setup's explicit order).
+      form "strata"  the XCD-strata form (csrc/bpr_strata.inc): the phases ceil(8 s_begin / nnz) up to, not including,
+                     ceil(8 (s_begin + n) / nnz) (8 at the end of the epoch); in phase ph virtual wave w draws
+                     len = |bucket (w, p)| times from its bucket p = ((w // 4) % 8 + ph) % 8 (strata_sample): the positive is
+                     rec_u / rec_i[base + r], the negative rank_item[code].  ownership = the tables of the strata grid's
+                     wave count; k picks UNR (strata_unr); hot_permille, hot_min_mult_x100, rehash_period = strata_config's.
 
     Returns a dict: u, i, j (int64 arrays, the restatement's order), skipped (the launch's skip count); "ldsbin" adds bin
     (the bin that drew each triplet) and hot (its positive came from the hot list); "owned" adds shared (its user is
-    split over the waves: atomics on its row)."""
+    split over the waves: atomics on its row); "strata" adds shared, hot_i / hot_j (the item row is updated by atomics),
+    wave, phase, step (tile x 64 + the triplet's group of UNR among the tile's valid draws, compacted in lane order), and
+    n_hot, key, buckets (sptr, rec_u, rec_i, rank_item), unr, phases (lo, hi)."""
     indptr = np.ascontiguousarray(indptr, np.int32)
     indices = np.ascontiguousarray(indices, np.int32)
     nnz, s_begin, n = len(indices), int(s_begin), int(n)
     assert 0 <= s_begin and n >= 0 and s_begin + n <= nnz
+    if form == "strata":
+        assert not neg_pop and ownership is not None and k is not None
+        return _strata_triplets(seed, epoch, s_begin, n, indptr, indices, n_items, ownership, int(k), hot_permille,
+                                hot_min_mult_x100, rehash_period)
     if form == "ldsbin":
         conveyor = deal is not None
         if conveyor:
@@ -772,7 +858,7 @@ def hogwild_triplets(form, seed, epoch, s_begin, n, indptr, indices, n_items, ne
         shared = u < 0
         u = np.where(shared, ~u, u)
     else:
-        raise ValueError("form is 'fused', 'owned' or 'ldsbin': %r" % (form,))
+        raise ValueError("form is 'fused', 'owned', 'ldsbin' or 'strata': %r" % (form,))
     j = indices[jj].astype(np.int64) if neg_pop else jj
     keep = ~_csr_has(indptr, indices, n_items, u, j)
     out = dict(u=u[keep], i=i[keep], j=j[keep], skipped=int((~keep).sum()))

@@ -1,7 +1,8 @@
 """Inputs, references and checks of the hogwild BPR step tests, in ONE place: tests/test_bpr_step_gpu.py runs the cases on
 the device, tests/test_bpr_step_cpu.py proves — from the restatements and the float64 step alone — that every case is a
 fair test, that the tolerances below follow their rules, and that the checks reject nine deliberately wrong updates (and,
-for the conveyor's block buffers, four wrong uses of them).
+for the conveyor's block buffers, four wrong uses of them; for the XCD-strata form, seven wrong merges, write paths and
+lane masks of its own, and two wrong racy rows).
 
 A case = Zipf interactions + normal tables with real scores (z well away from 0.5) + ONE launch of `n` samples at sample
 offset `s_begin` of epoch 0 (conveyor cases: ONE conveyor_enqueue over 1 to 8 blocks, whose item rows live in block
@@ -23,6 +24,15 @@ restatement's and two seeded permutations), float64, rounded up to one significa
 path by which ANY order of exact updates may differ from the Jacobi sum, so it bounds a correct kernel whatever its
 scheduling; a lost or doubled update moves a row by path / touches, visible where that exceeds 2 x the tolerance.
 tests/test_bpr_step_cpu.py asserts both rules and prints every figure.
+
+The XCD-strata form (csrc/bpr_strata.inc; a launch = one or two whole phases of an epoch) stores its cold item rows with
+plain read-modify-write among the CUs of one XCD, by design: of two waves that touch such a row in one phase, one may
+overwrite the other's store.  Launch B therefore holds a strata case under TWO rules (check_b_strata), the rows' classes
+decided on the CPU from the triplets alone: every U row, every hot item row and every cold item row that ONE wave per
+phase touches, each with its bias, under the rule above, unchanged — that class carries the in-step merge (UNR triplets
+of a wave share one load of a row; its lead reference stores every delta of the step) and the same-wave store-then-load
+order; a cold item row that two or more waves of a phase touch under the racy rule (racy_rows): element by element,
+got - start within tolerance / sqrt(k) of the sum of a non-empty subset of the row's (phase, wave, step) groups.
 """
 import functools
 
@@ -57,6 +67,20 @@ LR_A, LR_B, REG = 0.05, 2.0 ** -12, 0.01
 # MI355X, conveyor: `correct` inside the float64 interval in all 15 cases (one number in 13); launch A, clean rows: U 5.9e-8,
 #   V 5.9e-8, B 6.1e-8; launch B, error / tolerance: U 0.14, V 0.22 (conv_k40), B 0.59 (conv_k192; 0.43 conv_k40, 0.40
 #   conv_ranges8_k64: rows touched once, the floor term as above); layouts equal to the oracle's, no lock time-outs.
+# XCD strata (one phase of 4 096 / 5 120 / 7 168 waves at k <= 64 / <= 192 / above: 65 158 .. 65 961 triplets, two phases 131 000):
+#   float32 step vs float64 step over the clean rows 5.9e-8 .. 8.5e-8 (T_CLEAN stays); |sequential - jacobi| / path, three
+#   orders: 0.0046 .. 0.0097 (0.0137 two phases at k = 64, 0.0196 strata_rehash2_k100)  ->  C = 0.02 .. 0.08 below.  14 % of the
+#   triplets clean (6 % at 100 000 x 200 000, 20 % at 1 048 583 items); racy rows 10.6 .. 10.9 % of the touched item rows (13.2 %
+#   without hot items, 12.1 % over two phases, 23.2 % at 200 000 items, 4.1 % at 1 048 583), 2 .. 11 groups each; at UNR = 4 /
+#   2 some 4 200 / 2 000 steps name a cold item twice and 7 900 / 4 200 repeat an exclusive user, 3 000 / 2 500 are partial.
+# MI355X, strata: `correct` inside the float64 interval in all 16 cases (one number in 2); launch A, clean rows: U 6.1e-8,
+#   V 6.1e-8, B 8.5e-8; launch B, exact rule, error / tolerance: U 0.15 (strata_k33), V 0.19 (strata_k128), B 0.80
+#   (strata_k64; 0.75 strata_partial_k64); racy rule: every racy row passes; ONE
+#   subset explains 94 .. 97 % of them as a whole (9 585 of 9 991 at k = 64, 18 300 of 19 377 at k = 200: on the others the
+#   elements of one row come from different subsets, so two waves' stores of a row interleave below the row), and a third
+#   lost at least one group at UNR = 4 (3 342 of 9 991; 31 .. 35 % over the cases), 20 .. 24 % at UNR = 2, 13 % at UNR = 1 (2 529 of 19 377) — a phase of
+#   these launches is one tile per wave, every wave of the grid at once; packed and unpacked records alike (6 695 / 6 845 of
+#   20 424 at k = 64).  Hot set, epoch key and bucket tables equal to their restatements; misplaced workgroups 0 in every case.
 T_CLEAN = 5e-7
 C = {
     "fused_k3": 0.03, "fused_k7": 0.02, "fused_k16": 0.02, "fused_k20": 0.02,
@@ -69,6 +93,10 @@ C = {
     "conv_k40": 0.01, "conv_k64": 0.02, "conv_k100": 0.02, "conv_k192": 0.03, "conv_k256": 0.02,
     "conv_pop_k64": 0.02, "conv_pop_k100": 0.02, "conv_pop_k192": 0.02, "conv_pop_k256": 0.03, "conv_nobias_k192": 0.02,
     "conv_ranges3_k100": 0.02, "conv_ranges8_k64": 0.02, "conv_pad_k64": 0.02, "conv_order_k64": 0.02, "conv_heavy_k64": 0.03,
+    "strata_k33": 0.02, "strata_k64": 0.04, "strata_k100": 0.04, "strata_k128": 0.04, "strata_k192": 0.04, "strata_k200": 0.04,
+    "strata_allhot_k64": 0.03, "strata_allhot_k100": 0.03, "strata_nohot_k64": 0.03, "strata_packed_k64": 0.06,
+    "strata_packed_k100": 0.04, "strata_nobias_k100": 0.03, "strata_partial_k64": 0.03, "strata_epoch1_k64": 0.03,
+    "strata_rehash2_k100": 0.08, "strata_auto_k33": 0.02,
 }
 
 
@@ -102,7 +130,25 @@ def _conv_pop(k, **kw):
     return _conv(k, kind="pop", neg_pop=True, clean_share=False, **kw)
 
 
-# One case per kernel instantiation the dispatchers return (csrc/bpr.hip pick_hogwild_kernel, pick_ldsbin_kernel).
+def strata_waves(k, cus=MI355X_CUS):
+    """the strata kernel's persistent grid on an MI355X, in waves: 4 / 5 / 5 / 7 workgroups of 4 waves per CU for the
+    instantiations <1,4> / <2,2> / <3,2> / <4,1> (98 / 81 / 94 / 71 VGPRs of 512).  The device test takes the count from
+    debug_ownership() and rebuilds the case if the device runs another grid."""
+    return cus * 4 * (4 if k <= 64 else 5 if k <= 192 else 7)
+
+
+def _strata(k, **kw):
+    """ONE phase of the XCD-strata form (csrc/bpr_strata.inc): s_begin = the nominal start of `phase`, n = 1 (Case computes
+    both).  The form needs 33 <= k <= 256 and nnz >= CUs x 8 x 4 x 64, so the problem is the owned cases': a phase is an eighth
+    of the epoch, some 65 700 triplets, 14 % of them clean, and launch B carries the form (clean_share=False: the clean
+    triplets that exist are checked all the same).  hot_cfg = strata_config's (hot_permille, hot_min_mult_x100, rehash_period);
+    phases = 2: a second phase, enqueued by a second call without a sync in between; packed: chunk_records(True) first."""
+    return dict(dict(form="strata", k=k, nu=200_000, ni=400_000, nnz=524_288, zipf=0.3, n=1, phase=2, epoch=0, phases=1,
+                     flags=_lib.FORM_STRATA, clean_share=False, hot_cfg=(120, 200, 1), packed=False, racy_cap=0.15), **kw)
+
+
+# One case per kernel instantiation the dispatchers return (csrc/bpr.hip pick_hogwild_kernel, pick_ldsbin_kernel,
+# pick_strata_kernel).
 SPECS = {
     # fused, unowned: every (G, R) of the row-wise kernel, the generic kernel, two float4 layouts, the switches
     "fused_k3": _fused(3), "fused_k7": _fused(7), "fused_k16": _fused(16), "fused_k20": _fused(20),
@@ -153,9 +199,26 @@ SPECS = {
     "conv_order_k64": _conv(64, order_seed=77),  # conveyor_setup's explicit item order: a seeded permutation
     # skipped draws and hot user rows: 8 users of 600 interactions each on top (denser data would leave nothing clean)
     "conv_heavy_k64": _conv(64, kind="heavy", ni=65_536, heavy=(8, 600), clean_share=False),
+    # XCD strata (csrc/bpr.hip pick_strata_kernel): <1,4> at k = 33 and 64, <2,2> at 100 and 128, <3,2> at 192, <4,1> at 200
+    # (a 100 000 x 200 000 problem, so that its float64 tables are the size of owned_k100's; twice the rows race there)
+    "strata_k33": _strata(33), "strata_k64": _strata(64), "strata_k100": _strata(100), "strata_k128": _strata(128, seed=0x5EED0080),
+    "strata_k192": _strata(192), "strata_k200": _strata(200, nu=100_000, ni=200_000, racy_cap=0.30),
+    # every item hot: the whole launch goes through atomics and every row is under the exact rule; no item hot
+    "strata_allhot_k64": _strata(64, hot_cfg=(1000, 0, 1)), "strata_allhot_k100": _strata(100, hot_cfg=(1000, 0, 1)),
+    "strata_nohot_k64": _strata(64, hot_cfg=(0, 200, 1)),
+    # packed records (pitch kp + 32, bias at column kp): kp = 64, and kp = 128 with 28 pad columns; two phases, the second
+    # launched from the records the first left (the device test runs the same two phases unpacked as well)
+    "strata_packed_k64": _strata(64, packed=True, phases=2, phase=3), "strata_packed_k100": _strata(100, packed=True, phases=2, phase=6),
+    "strata_nobias_k100": _strata(100, use_bias=False),
+    "strata_partial_k64": _strata(64, ni=400_003, phase=5),  # 400 003 = 8 x 50 000 + 3: three partitions hold one item more
+    "strata_epoch1_k64": _strata(64, epoch=1, phase=0),  # the re-deal under the key of epoch 1
+    "strata_rehash2_k100": _strata(100, epoch=1, phase=7, hot_cfg=(120, 200, 2)),  # epoch 1 draws from the buckets of epoch 0's key
+    # flags = 0: 2^20 items and more, no LDS-bin plan -> the strata form by itself
+    "strata_auto_k33": _strata(33, ni=1_048_583, flags=0, phase=4),
 }
 NAMES = list(SPECS)
 CONVEYOR_NAMES = [name for name in NAMES if SPECS[name]["form"] == "conveyor"]
+STRATA_NAMES = [name for name in NAMES if SPECS[name]["form"] == "strata"]
 PAD = -7.75  # what the pad slots of the block buffers hold (finite: a pad slot read as a row shows in the checks, not as a NaN)
 
 
@@ -289,6 +352,20 @@ class Case:
             assert tmax * self.s_begin // self.nnz == 0 and (tmax == 1 or tmax * (self.s_begin + self.n) // self.nnz == 1)
             kw = dict(ownership=self.ownership)
         form, epoch = self.form, 0
+        if self.form == "strata":
+            assert self.nnz >= cus * 8 * 4 * 64 and 33 <= self.k <= 256
+            if self.flags == 0:  # FORM_AUTO takes the strata form by itself: 2^20 items and more, and no LDS-bin plan
+                assert self.ni >= 1 << 20 and ldsbin_plan(self.ni, self.nnz, self.k, cus) is None
+            self.waves = waves or strata_waves(self.k, cus)
+            self.ownership = orc.hogwild_ownership(self.indptr, self.indices, self.waves)
+            # phase ph begins at sample ceil(ph nnz / 8); the first call enqueues 1 sample there, every further call the samples
+            # up to and including the next phase's first one (csrc/bpr.hip strata_enqueue: a launch runs the phases that begin inside it)
+            first = [-(-(self.phase + q) * self.nnz // 8) for q in range(self.phases)]
+            assert self.phase + self.phases <= 8
+            self.s_begin, self.launch_ns = first[0], [1] + [b - a for a, b in zip(first, first[1:])]
+            self.n, epoch = sum(self.launch_ns), self.epoch
+            kw = dict(ownership=self.ownership, k=self.k, hot_permille=self.hot_cfg[0], hot_min_mult_x100=self.hot_cfg[1],
+                      rehash_period=self.hot_cfg[2])
         if self.form == "conveyor":
             self.plan = conveyor_plan(self.ni, self.k, self.n_blocks, cus, self.min_candidates)
             assert self.plan is not None, "%s: no conveyor plan" % name
@@ -313,6 +390,10 @@ class Case:
             self.draws = t["draws"]
         self.trip = (t["u"], t["i"], t["j"])
         self.skipped, self.hot, self.bin, self.shared = t["skipped"], t.get("hot"), t.get("bin"), t.get("shared")
+        self.racy = None
+        if self.form == "strata":
+            self.strata = t
+            self._classify_item_rows(t)
         # launch B: the Jacobi sum of every row; launch A: the float64 step of the clean triplets alone (their rows have no
         # other delta, so no sum is needed); launch Z: the float64 scores (they do not depend on lr)
         self.jac = step.jacobi(self.trip, self.tables, LR_B, REG, self.use_bias)
@@ -331,6 +412,57 @@ class Case:
             ("B", self.tables[2], cij, np.concatenate([dBi, dBj])))}
         self.x, self.z = self.jac["x"], self.jac["z"]
         self.x_bound = step.score_error_bound(self.trip, self.tables)
+
+    def _classify_item_rows(self, t):
+        """the classes of the strata form's item rows, from the triplets alone: hot (device-scope atomics), cold and touched
+        by ONE wave per phase (plain stores in program order), cold and touched by two or more waves of one phase (`racy`:
+        plain read-modify-write among the CUs of one XCD; two phases never race, the kernel boundary lies between them).  A
+        reference = one naming of an item row by a triplet (its i, then its j); its group = the (phase, wave, step) it is
+        loaded and stored in."""
+        W, n = self.waves, len(t["i"])
+        self.ref_row = np.concatenate([t["i"], t["j"]])
+        self.ref_hot = np.concatenate([t["hot_i"], t["hot_j"]])
+        self.ref_trip = np.concatenate([np.arange(n), np.arange(n)])
+        self.ref_isj = np.concatenate([np.zeros(n, bool), np.ones(n, bool)])
+        self.item_hot = np.zeros(self.total_items, bool)
+        self.item_hot[self.ref_row[self.ref_hot]] = True
+        assert not self.item_hot[self.ref_row[~self.ref_hot]].any(), "an item is hot in every reference or in none"
+        phase, wave = np.concatenate([t["phase"]] * 2), np.concatenate([t["wave"]] * 2)
+        pairs = np.unique((self.ref_row * 8 + phase) * W + wave)  # distinct (row, phase, wave)
+        rp, waves_of = np.unique(pairs // W, return_counts=True)  # per (row, phase)
+        self.racy = np.zeros(self.total_items, bool)
+        self.racy[np.unique(rp[waves_of >= 2] // 8)] = True
+        self.racy &= ~self.item_hot
+        self.trip_group = np.unique((t["phase"] * W + t["wave"]) * (1 << 24) + t["step"], return_inverse=True)[1]
+        self.ref_group = np.concatenate([self.trip_group] * 2)
+        self._racy_groups = None
+
+    def racy_groups(self):
+        """{m: (rows [n], dV [n, m, k], dB [n, m])}: the racy rows that m groups name, with every group's float64 delta of
+        launch B (the sum over the group's references of the row: what the in-step merge stores at once)"""
+        if self._racy_groups is not None:
+            return self._racy_groups
+        sel = np.flatnonzero(self.racy[self.ref_row])
+        if len(sel) == 0:
+            self._racy_groups = {}
+            return self._racy_groups
+        trips, inv = np.unique(self.ref_trip[sel], return_inverse=True)
+        _, _, _, dVi, dVj, dBi, dBj = step.deltas(tuple(a[trips] for a in self.trip), *self.tables, LR_B, REG, self.use_bias)
+        isj = self.ref_isj[sel]
+        dv, db = np.where(isj[:, None], dVj[inv], dVi[inv]), np.where(isj, dBj[inv], dBi[inv])
+        row, grp = self.ref_row[sel], self.ref_group[sel]
+        order = np.lexsort((grp, row))
+        row, grp, dv, db = row[order], grp[order], dv[order], db[order]
+        starts = np.flatnonzero(np.r_[True, (row[1:] != row[:-1]) | (grp[1:] != grp[:-1])])
+        gdv, gdb, grow = np.add.reduceat(dv, starts, axis=0), np.add.reduceat(db, starts), row[starts]
+        rows, first, m = np.unique(grow, return_index=True, return_counts=True)
+        out = {}
+        for mm in np.unique(m):
+            pick = np.flatnonzero(m == mm)
+            idx = first[pick][:, None] + np.arange(mm)[None, :]
+            out[int(mm)] = (rows[pick], gdv[idx], gdb[idx])
+        self._racy_groups = out
+        return out
 
     def triplets_of(self, table, row):
         u, i, j = self.trip
@@ -410,13 +542,14 @@ def tolerance_b(c, tab, coeff=None):
     return coeff * j["path"] + j["touches"] * half_ulp * np.sqrt(start.shape[1])
 
 
-def check_b(c, got, coeff=None):
-    """launch B: every touched row against the Jacobi sum.  Returns the largest error / tolerance per table."""
+def check_b(c, got, coeff=None, other_rule=None):
+    """launch B: every touched row against the Jacobi sum.  Returns the largest error / tolerance per table.  other_rule =
+    {table: mask of the rows that another rule holds} (check_b_strata: the racy rows)."""
     _untouched_identical(c, "B", got)
     worst = {}
     for tab, start, g in zip("UVB", c.tables, got):
         j = c.jac[tab]
-        rows = np.flatnonzero(j["touches"] > 0)
+        rows = np.flatnonzero((j["touches"] > 0) & ~other_rule[tab] if other_rule and tab in other_rule else j["touches"] > 0)
         if len(rows) == 0:
             worst[tab] = 0.0
             continue
@@ -442,3 +575,64 @@ def visibility(c, tab, coeff=None):
 def round_up_1sig(v):
     e = np.floor(np.log10(v))
     return float(np.ceil(v / 10 ** e - 1e-9) * 10 ** e)
+
+
+# ---- the XCD-strata form: launch B under two rules ----------------------------------------------------------------------------
+MAX_RACY_GROUPS = 16
+
+
+def racy_rows(c, got, coeff=None):
+    """The racy rule, row by row.  A cold item row that two or more waves of one phase touch is plain read-modify-write among
+    the CUs of one XCD: a store may overwrite another wave's, so what arrives is the sum of SOME of the row's (phase, wave,
+    step) groups — at least one, the last store's.  Element by element (nobody has measured at what granularity two waves'
+    stores of one row interleave), got - start must lie within the row's tolerance_b / sqrt(k) of the sum of a non-empty
+    subset of its groups' float64 deltas; the bias, one element, within its own tolerance_b.  Returns per racy row: rows,
+    groups, ok (the rule holds), whole (ONE subset explains the row and its bias), full (the subset of all groups does)."""
+    tol_v, tol_b = tolerance_b(c, "V", coeff) / np.sqrt(c.k), tolerance_b(c, "B", coeff)
+    out = dict(rows=[], groups=[], ok=[], whole=[], full=[])
+    for m, (rows, dv, db) in sorted(c.racy_groups().items()):
+        assert 2 <= m <= MAX_RACY_GROUPS, "%s: a racy row of %d groups" % (c.name, m)
+        subsets = ((np.arange(1, 1 << m)[:, None] >> np.arange(m)[None, :]) & 1).astype(np.float64)  # (the last one: all groups)
+        chunk = max(1, (1 << 22) // (len(subsets) * c.k))
+        for a in range(0, len(rows), chunk):
+            r = rows[a:a + chunk]
+            moved = got[1][r].astype(np.float64) - c.tables[1][r].astype(np.float64)
+            sums = np.einsum("sm,nmk->nsk", subsets, dv[a:a + chunk])
+            within = np.abs(moved[:, None, :] - sums) <= tol_v[r][:, None, None]
+            if c.use_bias:
+                moved_b = got[2][r].astype(np.float64) - c.tables[2][r].astype(np.float64)
+                within_b = np.abs(moved_b[:, None] - db[a:a + chunk] @ subsets.T) <= tol_b[r][:, None]
+            else:
+                within_b = np.ones(within.shape[:2], bool)
+            each = within.all(axis=2) & within_b
+            out["rows"].append(r)
+            out["groups"].append(np.full(len(r), m))
+            out["ok"].append(within.any(axis=1).all(axis=1) & within_b.any(axis=1))
+            out["whole"].append(each.any(axis=1))
+            out["full"].append(each[:, -1])
+    return {key: (np.concatenate(v) if v else np.zeros(0, bool if key in ("ok", "whole", "full") else np.int64))
+            for key, v in out.items()}
+
+
+def check_b_strata(c, got, coeff=None):
+    """launch B of a strata case: check_b, unchanged, on every U row, every hot item row and every cold item row that one
+    wave per phase touches (with their biases); the racy rule on the others.  Returns check_b's figures and: racy (rows
+    under the racy rule), whole (explained by one subset as a whole), lost (not explained by the sum of all their groups:
+    at least one group's store was overwritten)."""
+    worst = check_b(c, got, coeff, other_rule={"V": c.racy, "B": c.racy})
+    r = racy_rows(c, got, coeff)
+    bad = np.flatnonzero(~r["ok"])
+    assert len(bad) == 0, "launch B, racy rule: no subset of the row's %d groups explains an element (%d such rows of %d): %s" % (
+        r["groups"][bad[0]], len(bad), len(r["ok"]), c.describe("V", int(r["rows"][bad[0]])))
+    worst.update(racy=len(r["ok"]), whole=int(r["whole"].sum()), lost=int((~r["full"]).sum()))
+    return worst
+
+
+def racy_visible(c, coeff=None):
+    """per racy row (the order of racy_rows): a single group's loss shows, path / groups > 2 x tolerance"""
+    tol, path = tolerance_b(c, "V", coeff), c.jac["V"]["path"]
+    rows = [(r, np.full(len(r), m)) for m, (r, _, _) in sorted(c.racy_groups().items())]
+    if not rows:
+        return np.zeros(0, bool)
+    r, m = np.concatenate([a for a, _ in rows]), np.concatenate([b for _, b in rows])
+    return path[r] / m > 2 * tol[r]

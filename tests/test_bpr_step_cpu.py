@@ -68,6 +68,11 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
             assert (items < 0).sum() >= 100, "pad slots in the launched bins"
         if name == "conv_order_k64":
             assert not np.array_equal(c.rank_item, np.argsort(-np.bincount(c.indices, minlength=c.ni), kind="stable"))
+    elif c.form == "strata":  # every wave's whole bucket of the phase's partition, for every phase of the launch
+        sptr, w = c.strata["buckets"][0], np.arange(c.waves)
+        assert draws == sum(int((sptr[8 * w + ((w // 4) % 8 + ph) % 8 + 1] - sptr[8 * w + ((w // 4) % 8 + ph) % 8]).sum())
+                            for ph in range(*c.strata["phases"]))
+        assert c.strata["phases"] == (c.phase, c.phase + c.phases)
     else:  # one 64-sample tile of every wave's slice
         assert draws == np.minimum(np.diff(c.ownership[0]), 64).sum()
     for start in c.tables:
@@ -117,11 +122,86 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
               ", ".join("%s %.2f" % kv for kv in vis.items())))
     if not c.only_b:  # (the wide-tile case alone may fall below: its comment says why)
         assert min(vis.values()) >= 0.5, vis
+    if c.form == "strata":
+        _strata_case_is_fair(c, n_trip)
     if c.form == "owned":
         tu = c.touches["U"]
         assert tu[tu > 0].mean() < 4 and tv[tv > 0].mean() < 4, "few touches per row"
         assert c.shared.any() and not c.shared.all(), "exclusive users (plain stores) and shared ones (atomics) both occur"
         assert vis["U"] >= 0.5, vis
+
+
+_STRATA_SKIPPED = {}  # per strata case, filled as the cases go by
+
+
+def _repeats_in_a_step(group, row, n_rows):
+    """steps (groups) in which one row is named more than once"""
+    key, count = np.unique(group * n_rows + row, return_counts=True)
+    return len(np.unique(key[count > 1] // n_rows))
+
+
+def _strata_case_is_fair(c, n_trip):
+    """the conditions of a strata case, from the restatement alone: few enough racy rows that the exact rule carries the
+    case, enough in-step merges, hot and shared rows that every write path of the kernel is under a rule"""
+    t = c.strata
+    _STRATA_SKIPPED[c.name] = c.skipped
+    touched = int((c.touches["V"] > 0).sum())
+    racy = int(c.racy.sum())
+    groups = c.racy_groups()
+    cold = ~c.ref_hot
+    rep_cold = _repeats_in_a_step(c.ref_group[cold], c.ref_row[cold], c.total_items)
+    rep_hot = _repeats_in_a_step(c.ref_group[~cold], c.ref_row[~cold], c.total_items)
+    excl = ~c.shared
+    rep_user = _repeats_in_a_step(c.trip_group[excl], c.trip[0][excl], c.nu)
+    steps = int(c.trip_group.max()) + 1
+    partial = int((np.bincount(c.trip_group) < t["unr"]).sum())
+    vis = bc.racy_visible(c)
+    print("\n%s: %d waves, phases %s, %d triplets in %d steps of %d (%d partial, %d in a second tile); n_hot %d, %d hot positives, %d hot "
+          "negatives, %d shared-user triplets; steps with a repeated cold item %d, hot item %d, exclusive user %d; racy rows %d of "
+          "%d touched = %.1f %% (cap %.0f %%), groups per racy row %s, one lost group visible on %.2f of them" % (
+              c.name, c.waves, t["phases"], n_trip, steps, t["unr"], partial, int((t["step"] >= 64).sum()), t["n_hot"],
+              int(t["hot_i"].sum()), int(t["hot_j"].sum()), int(c.shared.sum()), rep_cold, rep_hot, rep_user, racy, touched,
+              100.0 * racy / touched, 100 * c.racy_cap, {m: len(v[0]) for m, v in sorted(groups.items())},
+              vis.mean() if len(vis) else 1.0))
+    assert t["unr"] == (4 if c.k <= 64 else 2 if c.k <= 192 else 1)
+    assert racy <= c.racy_cap * touched, (racy, touched)
+    assert not groups or max(groups) <= bc.MAX_RACY_GROUPS, sorted(groups)
+    assert (c.touches["V"][c.racy] >= 2).all() and not c.item_hot[c.racy].any()
+    all_hot, no_hot = c.hot_cfg[:2] == (1000, 0), c.hot_cfg[0] == 0
+    if all_hot:  # every item hot: no cold row to merge or to race; the atomics carry the repeats
+        assert t["n_hot"] == c.ni and t["hot_i"].all() and t["hot_j"].all() and racy == 0
+        assert t["unr"] == 1 or (rep_hot >= 1000 and rep_user >= 1000), (rep_hot, rep_user)
+    elif t["unr"] > 1:
+        assert rep_cold >= 1000 and rep_user >= 1000, (rep_cold, rep_user)
+    if no_hot:
+        assert t["n_hot"] == 0 and not t["hot_i"].any() and not t["hot_j"].any()
+    elif not all_hot:
+        assert 0 < t["n_hot"] < c.ni and t["hot_i"].sum() >= 1000 and t["hot_j"].sum() >= 1000
+    assert c.shared.any() and not c.shared.all()
+    assert (np.bincount(c.trip_group) <= t["unr"]).all()
+    if c.name == "strata_partial_k64":  # three partitions hold an item more than the others
+        sizes = np.bincount(orc_partitions(c), minlength=8)
+        assert c.ni % 8 == 3 and sorted(sizes.tolist()) == [c.ni // 8] * 5 + [c.ni // 8 + 1] * 3
+    if c.name == "strata_rehash2_k100":
+        from oracle import oracle as orc
+
+        assert t["key"] == orc.strata_key(c.seed, 0) != orc.strata_key(c.seed, 1)
+    if c.name == "strata_epoch1_k64":
+        from oracle import oracle as orc
+
+        assert t["key"] == orc.strata_key(c.seed, 1) != orc.strata_key(c.seed, 0)
+
+
+def orc_partitions(c):
+    from oracle import oracle as orc
+
+    return orc.strata_partitions(c.strata["key"], c.ni)
+
+
+def test_the_strata_cases_hold_a_skipped_draw(oracle):
+    skipped = {name: _STRATA_SKIPPED[name] if name in _STRATA_SKIPPED else bc.case(name).skipped for name in bc.STRATA_NAMES}
+    print("\nskipped draws of the strata cases: %s" % skipped)
+    assert sum(skipped.values()) >= 1
 
 
 def test_t_clean_follows_its_rule(oracle):
@@ -295,3 +375,118 @@ def test_checks_reject_a_written_pad_slot(oracle):
         bufs[blk][at] = 0.0
         with pytest.raises(AssertionError, match="pad slot"):
             bc.conveyor_tables(c, "B", bufs, U)
+
+
+# ---- the XCD-strata form: its own ways of being wrong, each built from the float64 step on the case's own triplets ----------
+STRATA_MUTANTS = {  # fault -> the case it is shown on
+    "lead_of_a_repeated_cold_row_stores_its_own_delta": "strata_k64",
+    "every_reference_of_a_repeated_cold_row_adds_the_total": "strata_k64",
+    "last_delta_of_a_repeated_exclusive_user_only": "strata_k64",
+    "negative_bias_delta_with_the_positive_sign": "strata_k64",
+    "hot_rows_written_by_their_last_toucher": "strata_k64",
+    "bias_written_one_row_off": "strata_k64",
+    "lanes_from_64_of_an_r2_row_left_out": "strata_k100",
+}
+_MERGE_FAULTS = list(STRATA_MUTANTS)[:3] + ["hot_rows_written_by_their_last_toucher"]  # (they change no clean row: launch B's to find)
+
+
+def _keep_one_per_key(key, order, which):
+    """mask over the references: the first / last one (by `order`) of every key"""
+    o = np.lexsort((order, key))
+    ks = key[o]
+    edge = np.r_[True, ks[1:] != ks[:-1]] if which == "first" else np.r_[ks[1:] != ks[:-1], True]
+    keep = np.zeros(len(key), bool)
+    keep[o[edge]] = True
+    return keep
+
+
+def _strata_host_launch(c, lr, fault=None):
+    """float64 (U, V, B) after the launch as a strata kernel with `fault` would leave them: every triplet's deltas from the
+    start tables (the Jacobi sum the checks hold the device to), each reference's delta weighted or moved as the fault says"""
+    u, i, j = c.trip
+    n = len(u)
+    _, z, dU, dVi, dVj, dBi, dBj = step.deltas(c.trip, *c.tables, lr, bc.REG, c.use_bias)
+    w_u, w_v = np.ones(n), np.ones(2 * n)  # per triplet; per item reference (the i's, then the j's)
+    in_step = 2 * c.ref_trip + c.ref_isj  # the order of the references: triplet by triplet, i before j
+    if fault in ("lead_of_a_repeated_cold_row_stores_its_own_delta", "every_reference_of_a_repeated_cold_row_adds_the_total"):
+        cold = np.flatnonzero(~c.ref_hot)
+        key = c.ref_group[cold] * c.total_items + c.ref_row[cold]  # (step, row)
+        if fault.startswith("lead"):
+            w_v[cold[~_keep_one_per_key(key, in_step[cold], "first")]] = 0.0
+        else:
+            _, inv, count = np.unique(key, return_inverse=True, return_counts=True)
+            w_v[cold] = count[inv]
+    elif fault == "last_delta_of_a_repeated_exclusive_user_only":
+        excl = np.flatnonzero(~c.shared)
+        w_u[excl[~_keep_one_per_key(c.trip_group[excl] * c.nu + u[excl], excl, "last")]] = 0.0
+    elif fault == "hot_rows_written_by_their_last_toucher":
+        hot = np.flatnonzero(c.ref_hot)
+        w_v[hot[~_keep_one_per_key(c.ref_row[hot], in_step[hot], "last")]] = 0.0
+    elif fault == "negative_bias_delta_with_the_positive_sign":
+        dBj = lr * (z - bc.REG * c.tables[2][j].astype(np.float64))
+    elif fault == "lanes_from_64_of_an_r2_row_left_out":
+        assert 64 < c.k <= 128
+        dU[:, 64:], dVi[:, 64:], dVj[:, 64:] = 0.0, 0.0, 0.0
+    else:
+        assert fault in (None, "bias_written_one_row_off"), fault
+    U, V, B = (np.array(t, np.float64) for t in c.tables)
+    np.add.at(U, u, dU * w_u[:, None])
+    np.add.at(V, i, dVi * w_v[:n, None])
+    np.add.at(V, j, dVj * w_v[n:, None])
+    off = 1 if fault == "bias_written_one_row_off" else 0
+    np.add.at(B, i + off, dBi * w_v[:n])
+    np.add.at(B, j + off, dBj * w_v[n:])
+    return U, V, B
+
+
+def test_the_unmutated_strata_launch_passes_every_check_and_a_lost_store_passes_the_racy_rule(oracle):
+    c = bc.case("strata_k64")
+    bc.check_z(c, c.tables, int((c.x > 0).sum()), c.skipped)
+    worst_a = bc.check_a(c, _as_device(step.sequential(c.trip, c.tables, bc.LR_A, bc.REG, True)))
+    for got in (step.sequential(c.trip, c.tables, bc.LR_B, bc.REG, True), _strata_host_launch(c, bc.LR_B)):
+        worst_b = bc.check_b_strata(c, _as_device(got))
+        assert worst_b["racy"] == c.racy.sum() == worst_b["whole"] and worst_b["lost"] == 0, worst_b
+    # every racy row keeps its LAST group only (each store overwrote the one before): the racy rule accepts, the exact one does not
+    U, V, B = _strata_host_launch(c, bc.LR_B)
+    for m, (rows, dv, db) in c.racy_groups().items():
+        V[rows] = c.tables[1][rows].astype(np.float64) + dv[:, -1]
+        B[rows] = c.tables[2][rows].astype(np.float64) + db[:, -1]
+    lost = bc.check_b_strata(c, _as_device((U, V, B)))
+    assert lost["whole"] == lost["racy"] and lost["lost"] > 0.9 * lost["racy"], lost
+    assert _fails(bc.check_b, c, _as_device((U, V, B)))
+    print("\nstrata_k64, sequential float64 reference rounded to float32: A %s, B %s; every racy row down to one group: %s" % (
+        worst_a, worst_b, lost))
+
+
+@pytest.mark.parametrize("mutant", list(STRATA_MUTANTS))
+def test_checks_reject_a_wrong_strata_update(oracle, mutant):
+    c = bc.case(STRATA_MUTANTS[mutant])
+    out = {}
+    for launch, lr in (("A", bc.LR_A), ("B", bc.LR_B)):
+        got = _as_device(_strata_host_launch(c, lr, mutant))
+        out[launch] = _fails(bc.check_a if launch == "A" else bc.check_b_strata, c, got)
+    print("\n%s, %s: rejected by %s" % (c.name, mutant, " and ".join(k for k, v in out.items() if v) or "NOTHING"))
+    assert out["A"] or out["B"], mutant
+    if mutant in _MERGE_FAULTS:
+        assert out["B"], "only launch B looks at rows touched more than once"
+
+
+@pytest.mark.parametrize("name", ["strata_k64", "strata_k200"])
+@pytest.mark.parametrize("mutant", ["every_group_scaled_by_2", "row_left_at_its_start_value"])
+def test_the_racy_rule_rejects_a_wrong_racy_row(oracle, name, mutant):
+    """both faults on EVERY racy row at once: the rule must reject at least nine tenths of the rows on which one group shows
+    at all (path / groups > 2 x tolerance)"""
+    c = bc.case(name)
+    U, V, B = _strata_host_launch(c, bc.LR_B)
+    rows = np.flatnonzero(c.racy)
+    scale = 2.0 if mutant == "every_group_scaled_by_2" else 0.0
+    V[rows] = c.tables[1][rows] + scale * c.jac["V"]["sum"][rows]
+    B[rows] = c.tables[2][rows] + scale * c.jac["B"]["sum"][rows]
+    r = bc.racy_rows(c, _as_device((U, V, B)))
+    visible = bc.racy_visible(c)
+    assert len(visible) == len(r["ok"]) == len(rows) and np.array_equal(np.sort(r["rows"]), rows)
+    rejected = float((~r["ok"][visible]).mean())
+    print("\n%s, %s: one group shows on %.3f of the %d racy rows; the racy rule rejects %.3f of those (%.3f of all)" % (
+        name, mutant, visible.mean(), len(rows), rejected, (~r["ok"]).mean()))
+    assert visible.mean() >= 0.5 and rejected >= 0.9
+    assert _fails(bc.check_b_strata, c, _as_device((U, V, B)))

@@ -2,7 +2,8 @@
 dispatchers return runs one short launch three times (tests/bpr_step_cases.py: Z at lr = 0, A at lr = 0.05 on the rows of
 clean triplets, B at lr = 2^-12 on every touched row), and the triplets of that launch are known beforehand from the CPU
 restatements of the samplers.  tests/test_bpr_step_cpu.py proves the cases fair and the checks sharp.  The conveyor's
-launches (cornac_hip_bpr_conveyor_enqueue: the rows in block buffers) run under the same three rules in a test of their own."""
+launches (cornac_hip_bpr_conveyor_enqueue: the rows in block buffers) run under the same three rules in a test of their own,
+and so do the XCD-strata form's phases, whose launch B holds the cold item rows that two waves touch under a rule of their own."""
 import numpy as np
 import pytest
 
@@ -25,7 +26,7 @@ def _launch(tr, c, lr):
     return tr.get_factors(), correct, skipped
 
 
-@pytest.mark.parametrize("name", [name for name in bc.NAMES if name not in bc.CONVEYOR_NAMES])
+@pytest.mark.parametrize("name", [name for name in bc.NAMES if name not in bc.CONVEYOR_NAMES + bc.STRATA_NAMES])
 def test_hogwild_launch_matches_the_float64_step(oracle, name):
     cus = _lib.device_info(0)["compute_units"]
     c = bc.case(name, cus)
@@ -63,6 +64,92 @@ def test_hogwild_launch_matches_the_float64_step(oracle, name):
           "B error / tolerance U %.3g V %.3g B %.3g (C %.3g)" % (
               name, len(c.trip[0]), z["correct"], z["lo"], z["hi"], a["U"], a["V"], a["B"], bc.T_CLEAN, b["U"], b["V"], b["B"],
               bc.C[name]))
+
+
+def _strata_launch(tr, c, lr, packed):
+    """the launch of a strata case from its start tables: (tables, correct, skipped).  One hogwild_enqueue per phase, no
+    sync in between: with packed records (chunk_records) the second phase starts from the records the first left."""
+    tr.chunk_records(packed)
+    tr.set_factors(*c.tables)
+    tr.seed_hogwild(c.seed)
+    args = (c.use_bias, c.neg_population, c.flags)
+    if c.epoch or c.s_begin:  # the earlier phases at lr = 0 move the sample counter and touch nothing (launch Z shows that)
+        tr.hogwild_enqueue(c.epoch * c.nnz + c.s_begin, 0.0, 0.0, *args)
+        tr.sync()
+    for n in c.launch_ns:
+        tr.hogwild_enqueue(n, lr, bc.REG if lr else 0.0, *args)
+    correct, skipped = tr.sync()
+    return tr.get_factors(), correct, skipped
+
+
+@pytest.mark.parametrize("name", bc.STRATA_NAMES)
+def test_strata_launch_matches_the_float64_step(oracle, name):
+    """The XCD-strata form (csrc/bpr_strata.inc) phase by phase.  Before anything is launched the device's hot set, epoch
+    key and bucket tables are held against their restatements; then launches Z, A and B, B under two rules
+    (bpr_step_cases.check_b_strata: cold item rows that two waves of a phase touch may lose a store, everything else is
+    exact)."""
+    cus = _lib.device_info(0)["compute_units"]
+    c = bc.case(name, cus)
+    tr = _lib.BprTrainer(c.indptr, c.indices, c.nu, c.ni, c.nu, c.total_items, c.k)
+    try:
+        tr.strata_config(*c.hot_cfg)
+        tr.seed_hogwild(c.seed)
+        if c.flags == 0:  # automatic dispatch: one sample at lr = 0 under flags = 0 must have built buckets for the strata kernel
+            assert tr.ldsbin_stats()["bins"] == 0, "%s: an LDS-bin plan exists" % name
+            tr.hogwild_enqueue(1, 0.0, 0.0, c.use_bias, c.neg_population, 0)
+            tr.sync()
+            st = tr.strata_stats()
+            assert st["waves"] > 0 and st["bucket_builds"] == 1, "%s: flags = 0 did not take the strata form: %r" % (name, st)
+            tr.seed_hogwild(c.seed)
+        sptr, rec_u, rec_i, rank_item, key = tr.debug_strata(c.epoch)
+        own = tr.debug_ownership()
+        assert own is not None, "%s: expected user-row ownership" % name
+        waves = len(own[0]) - 1
+        if waves != c.waves:  # another persistent grid than the case assumed: other triplets
+            c = bc.case(name, cus, waves)  # (C[name] was measured for the other launch)
+        for mine, dev in zip(c.ownership, own):
+            assert np.array_equal(mine, dev), "%s: the ownership tables differ from their restatement" % name
+        st = tr.strata_stats()
+        assert st["n_hot"] == c.strata["n_hot"], "%s: n_hot %d, restatement %d" % (name, st["n_hot"], c.strata["n_hot"])
+        assert key == c.strata["key"], "%s: the epoch key differs from its restatement" % name
+        for what, mine, dev in zip(("sptr", "rec_u", "rec_i", "rank_item"), c.strata["buckets"], (sptr, rec_u, rec_i, rank_item)):
+            assert np.array_equal(mine, dev), "%s: %s differs from its restatement" % (name, what)
+        builds = st["bucket_builds"]
+        got, correct, skipped = _strata_launch(tr, c, 0.0, c.packed)
+        z = bc.check_z(c, got, correct, skipped)
+        a = bc.check_a(c, _strata_launch(tr, c, bc.LR_A, c.packed)[0])
+        b = bc.check_b_strata(c, _strata_launch(tr, c, bc.LR_B, c.packed)[0])
+        unpacked = bc.check_b_strata(c, _strata_launch(tr, c, bc.LR_B, False)[0]) if c.packed else None
+        st = tr.strata_stats()
+        assert st["waves"] == waves and tr.debug_ownership()[0].shape == own[0].shape
+        if c.hot_cfg[2] > 1:  # epochs 0 and 1 share a key: the buckets built for the comparison above served every launch
+            assert st["bucket_builds"] == builds, (st, builds)
+    finally:
+        tr.close()
+    print("\n%s: %d waves, %d triplets, correct %d in [%d, %d]; A clean-row error U %.3g V %.3g B %.3g (T_CLEAN %.3g); "
+          "B error / tolerance, exact rule U %.3g V %.3g B %.3g (C %.3g); racy rows %d, explained whole %d, lost a group %d%s; "
+          "misplaced workgroups %d" % (
+              name, waves, len(c.trip[0]), z["correct"], z["lo"], z["hi"], a["U"], a["V"], a["B"], bc.T_CLEAN, b["U"], b["V"], b["B"],
+              bc.C[name], b["racy"], b["whole"], b["lost"],
+              "" if unpacked is None else " (unpacked: V %.3g B %.3g, whole %d, lost %d)" % (
+                  unpacked["V"], unpacked["B"], unpacked["whole"], unpacked["lost"]), st["misplaced_workgroups"]))
+
+
+def test_strata_config_refuses_what_it_cannot_run():
+    rs = np.random.RandomState(0)
+    indptr = np.arange(0, 4 * 1000 + 1, 4, dtype=np.int32)
+    indices = np.sort(rs.randint(0, 8192, (1000, 4)), axis=1).astype(np.int32)
+    indices += np.arange(4, dtype=np.int32)  # (strictly ascending within a user)
+    tr = _lib.BprTrainer(indptr, indices.ravel(), 1000, 8196, 1000, 8196, 64)
+    try:
+        for bad, what in (((-1, 200, 1), "hot_permille"), ((1001, 200, 1), "hot_permille"), ((120, -1, 1), "hot_min_mult_x100"),
+                          ((120, 200, 0), "rehash_period")):
+            with pytest.raises(_lib.HipError, match=what):
+                tr.strata_config(*bad)
+        tr.strata_config(0, 0, 1)
+        tr.strata_config(1000, 200, 3)
+    finally:
+        tr.close()
 
 
 def _conveyor_launch(tr, c, lr):
