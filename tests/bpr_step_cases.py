@@ -2,7 +2,7 @@
 the device, tests/test_bpr_step_cpu.py proves — from the restatements and the float64 step alone — that every case is a
 fair test, that the tolerances below follow their rules, and that the checks reject nine deliberately wrong updates (and,
 for the conveyor's block buffers, four wrong uses of them; for the XCD-strata form, seven wrong merges, write paths and
-lane masks of its own, and two wrong racy rows).
+lane masks of its own, and two wrong racy rows; for the resident exchange, eight wrong protocols of publishing and applying).
 
 A case = Zipf interactions + normal tables with real scores (z well away from 0.5) + ONE launch of `n` samples at sample
 offset `s_begin` of epoch 0 (conveyor cases: ONE conveyor_enqueue over 1 to 8 blocks, whose item rows live in block
@@ -33,6 +33,16 @@ phase touches, each with its bias, under the rule above, unchanged — that clas
 of a wave share one load of a row; its lead reference stores every delta of the step) and the same-wave store-then-load
 order; a cold item row that two or more waves of a phase touch under the racy rule (racy_rows): element by element,
 got - start within tolerance / sqrt(k) of the sum of a non-empty subset of the row's (phase, wave, step) groups.
+
+The resident exchange (the EXCH instantiations of csrc/bpr_ldsbin.inc; a launch = the WHOLE epoch, driven through
+cornac_amd.dist.ShardedBprTrainer on one rank without a process group) is held under launch Z, A and B as above and, in
+launch B, under a second rule on what the launch PUBLISHES (check_exch_b): P = sum over the exchanges of keeps + (table -
+base) is what the other ranks receive plus what the closing exchange still owes them, and every touched item row and bias
+of P lies within tolerance_b of the Jacobi sum, n_ex more roundings in its floor term; only hot rows may differ from their
+base afterwards, bucket e holds keep e (twice it where a twin rank is played on the communication stream) with the rule's
+weights, and base - start is the sum of the keeps.  With a twin under the "sqrt" rule the corrections c = rule(S) - keep are
+not zero and reach a row whenever the run lets them: the table rule gives way to the accounting, from the buffers read
+back — table - start - sum c = P and base - start - sum c = sum keeps — and P is held to the Jacobi sum under a C of its own.
 """
 import functools
 
@@ -81,6 +91,23 @@ LR_A, LR_B, REG = 0.05, 2.0 ** -12, 0.01
 #   lost at least one group at UNR = 4 (3 342 of 9 991; 31 .. 35 % over the cases), 20 .. 24 % at UNR = 2, 13 % at UNR = 1 (2 529 of 19 377) — a phase of
 #   these launches is one tile per wave, every wave of the grid at once; packed and unpacked records alike (6 695 / 6 845 of
 #   20 424 at k = 64).  Hot set, epoch key and bucket tables equal to their restatements; misplaced workgroups 0 in every case.
+# Resident exchange (a launch = the whole epoch: 299 977 .. 299 999 triplets, 1 .. 23 draws skipped; plans 1 024 bins of 293 / 157 / 108
+#   / 79 rows, 256 bins of 256 / 257; 2.5 (300 000 items) .. 9.2 (65 536) touches of a touched item row; 60 .. 103 triplets with a hot
+#   positive on 1 .. 3 hot items, 508 .. 547 on 19 at k = 100, 1 268 / 1 371 on 46 at k = 192, 2 853 / 2 933 on 101 at k = 200 / 256;
+#   0 .. 1 398 clean triplets): float32 step vs float64 step over the clean rows 2.8e-8 .. 6.1e-8; |sequential - jacobi| / path,
+#   three orders: 0.0020 without biases, 0.0052 .. 0.0100  ->  C = 0.009, 0.03 .. 0.04; the "sqrt" twin, |P - jacobi| / path over three
+#   host runs of the protocol (an exchange applied 0, 1, n_ex boundaries after its publication): 0.0097  ->  C = 0.04 (the order
+#   share of that case alone: 0.0075).  One lost update shows on >= 0.82 of the touched rows of every table (n_ex = 32 and the twin,
+#   C = 0.04 over 9.2 touches; 0.92 at k = 192 / 256 with popularity negatives; >= 0.95 elsewhere).
+# MI355X, resident exchange: `correct` inside the float64 interval in all 17 cases; launch A, clean rows: U 5.9e-8, V 5.7e-8, B
+#   6.1e-8; launch B, table rule, error / tolerance: U 0.24 (exch_k40), V 0.24, B 0.92 (exch_k64: bias rows touched once, the floor
+#   term as above; 0.35 and less elsewhere); published-delta rule: V 0.21, B 0.24 (exch_pop_k256); base - start - sum of keeps
+#   within 0.2 of its floor, the twin accounting within 0.31 .. 0.38; "align" weights within 0.03 of (k + 2) 2^-24; exchanges applied
+#   inside the launch: 0 .. 3 of 4, 1 .. 7 of 8, 0 .. 24 of 32, none of 11 (ex_per = 0) — the flush applies the others; rows apart
+#   from their base afterwards: exactly the n_hot hot rows on the 1 024-bin plans, none on the 256-bin ones; no lock time-outs.
+#   The floor of the identities takes max |row| = |start| + path (tolerance_b(reach=True)): with the start-and-end ulp a bias of
+#   5e-6 carried to 1e-4 and back missed it, 1.1e-11 against 2.5e-12 (exch_align_k100, bias 73 025), 9.1e-13 against 6.8e-13
+#   (exch_pop_k256, bias 21 132) — float32 roundings at the ulp of where the row has been, which C x path covers in the rules.
 T_CLEAN = 5e-7
 C = {
     "fused_k3": 0.03, "fused_k7": 0.02, "fused_k16": 0.02, "fused_k20": 0.02,
@@ -97,6 +124,11 @@ C = {
     "strata_allhot_k64": 0.03, "strata_allhot_k100": 0.03, "strata_nohot_k64": 0.03, "strata_packed_k64": 0.06,
     "strata_packed_k100": 0.04, "strata_nobias_k100": 0.03, "strata_partial_k64": 0.03, "strata_epoch1_k64": 0.03,
     "strata_rehash2_k100": 0.08, "strata_auto_k33": 0.02,
+    "exch_k64": 0.03, "exch_k100": 0.04, "exch_k192": 0.04, "exch_k200": 0.03, "exch_pop_k64": 0.03, "exch_pop_k100": 0.03,
+    "exch_pop_k192": 0.04, "exch_pop_k256": 0.03, "exch_k40": 0.03, "exch_nobias_k64": 0.009, "exch_partial_k64": 0.03,
+    "exch_one_k64": 0.03, "exch_ex32_k64": 0.04, "exch_short_k64": 0.03, "exch_align_k100": 0.03,
+    "exch_twin_sqrt_k64": 0.04,  # (its own rule: the share of three host runs of the protocol, tests/test_bpr_step_cpu.py)
+    "exch_twin_align_k100": 0.03,
 }
 
 
@@ -112,6 +144,22 @@ def _owned(k, **kw):
 
 def _lds(k, **kw):
     return dict(dict(form="ldsbin", k=k, nu=20_000, ni=30_720, nnz=300_000, zipf=0.8, n=2048, flags=_lib.FORM_LDSBIN), **kw)
+
+
+def _exch(k, **kw):
+    """ONE resident-exchange launch (csrc/bpr_ldsbin.inc, EXCH instantiations; cornac_amd.dist.ShardedBprTrainer.run_epoch with
+    resident = True): the WHOLE epoch, s_begin = 0 and n = nnz (Case sets n), with n_ex exchange points inside it.  A plan needs
+    nnz >= CUs x 16 x 64 = 262 144, so the launch is 300 000 draws and the catalogue as large as the LDS lets a resident plan
+    be: rows are touched few times and one lost update shows.  Next to no triplet of a whole epoch is clean (clean_share=False:
+    the clean triplets that exist are checked all the same) and launch B carries the family.  rule: the exchange's delta rule;
+    twin: a second rank with the same deltas is played on the communication stream (bucket *= 2)."""
+    return dict(dict(form="ldsbin", exch=True, k=k, nu=200_000, ni=300_000, nnz=300_000, zipf=0.3, user_sigma=0.5, n=None, s_begin=0,
+                     flags=_lib.FORM_LDSBIN, clean_share=False, n_ex=4, rule="sqrt", twin=False), **kw)
+
+
+def _exch256(k, **kw):
+    # 100 000 x 65 536: 256 bins of 256 rows, 1 172 draws = 37 tiles of 32 per bin
+    return _exch(k, **dict(dict(nu=100_000, ni=65_536, n_ex=8), **kw))
 
 
 def _conv(k, **kw):
@@ -215,8 +263,23 @@ SPECS = {
     "strata_rehash2_k100": _strata(100, epoch=1, phase=7, hot_cfg=(120, 200, 2)),  # epoch 1 draws from the buckets of epoch 0's key
     # flags = 0: 2^20 items and more, no LDS-bin plan -> the strata form by itself
     "strata_auto_k33": _strata(33, ni=1_048_583, flags=0, phase=4),
+    # the resident exchange (csrc/bpr.hip pick_ldsbin_kernel(exch = true)): R = 1..4 with uniform and with popularity negatives;
+    # the wide instantiations take 1 024 bins (the largest catalogue whose rows fit the LDS in four rounds)
+    "exch_k64": _exch(64), "exch_k100": _exch(100, ni=160_000), "exch_k192": _exch(192, ni=110_000), "exch_k200": _exch(200, ni=80_000),
+    "exch_pop_k64": _exch(64, neg_pop=True), "exch_pop_k100": _exch(100, ni=160_000, neg_pop=True),
+    "exch_pop_k192": _exch(192, ni=110_000, neg_pop=True), "exch_pop_k256": _exch(256, ni=80_000, neg_pop=True, seed=0x5EED0100),
+    "exch_k40": _exch256(40),  # R = 1 with lanes beyond k
+    "exch_nobias_k64": _exch256(64, use_bias=False),
+    "exch_partial_k64": _exch256(64, ni=65_549),  # 65 549 = 256 x 256 + 13: a partial last group, 257 rows per bin
+    "exch_one_k64": _exch256(64, n_ex=1),  # only the end-of-launch duty
+    "exch_ex32_k64": _exch256(64, n_ex=32),  # kLbMaxExchanges: 37 tiles per bin, so ex_per = 1 and ex_parts = 1
+    "exch_short_k64": _exch(64, n_ex=11),  # 10 tiles per bin: ex_per = 0, every boundary is met at the end of the launch
+    "exch_align_k100": _exch(100, ni=160_000, rule="align"),
+    # a twin rank: S = 2 d.  "align": the factor is exactly 1 / 2 and c an exact zero; "sqrt": c = (sqrt(2) - 1) d, the accounting
+    "exch_twin_sqrt_k64": _exch256(64, twin=True), "exch_twin_align_k100": _exch(100, ni=160_000, rule="align", twin=True),
 }
 NAMES = list(SPECS)
+EXCH_NAMES = [name for name in NAMES if SPECS[name].get("exch")]
 CONVEYOR_NAMES = [name for name in NAMES if SPECS[name]["form"] == "conveyor"]
 STRATA_NAMES = [name for name in NAMES if SPECS[name]["form"] == "strata"]
 PAD = -7.75  # what the pad slots of the block buffers hold (finite: a pad slot read as a row shows in the checks, not as a NaN)
@@ -328,7 +391,8 @@ class Case:
 
     def __init__(self, name, cus=MI355X_CUS, waves=None):
         sp = dict(dict(use_bias=True, neg_pop=False, s_begin=12_345, seed=0x5EED0000 + len(name), max_rounds=4,
-                       min_candidates=48, clean_share=True, only_b=False, user_sigma=1.0, heavy=None, kind=None), **SPECS[name])
+                       min_candidates=48, clean_share=True, only_b=False, user_sigma=1.0, heavy=None, kind=None, exch=False,
+                       n_ex=0, rule="sqrt", twin=False), **SPECS[name])
         self.name, self.spec = name, sp
         for key, v in sp.items():
             setattr(self, key, v)
@@ -343,6 +407,13 @@ class Case:
             self.plan = ldsbin_plan(self.ni, self.nnz, self.k, cus, self.min_candidates, self.max_rounds)
             assert self.plan is not None, "%s: no LDS-bin plan" % name
             kw = dict(n_bins=self.plan["bins"], share=self.nnz / (4.0 * cus) if self.plan["passing"] else None)
+        if self.exch:  # the whole epoch; the hot items (their rows stay in the global table: the atomic branch of ex_row_duty)
+            assert not self.plan["passing"] and self.s_begin == 0 and 1 <= self.n_ex <= 32
+            self.n = self.nnz
+            self.lds_tables = orc.ldsbin_tables(self.indptr, self.indices, self.ni, self.plan["bins"], 75)
+            self.n_hot = int(self.lds_tables["n_hot"])
+            self.hot_items = np.sort(self.lds_tables["rank_item"][:self.n_hot].astype(np.int64))
+            kw["tables"] = self.lds_tables
         if self.form == "owned":
             # the smallest launch of this form: one 64-sample tile of every wave (csrc/bpr.hip: a launch covers the tiles
             # [tmax s_begin / nnz, tmax (s_begin + n) / nnz) of every wave's slice, tmax = the longest slice's tile count)
@@ -464,6 +535,30 @@ class Case:
         self._racy_groups = out
         return out
 
+    def exch_tiles(self):
+        """per bin of a resident-exchange launch: (draws, tile width, tiles), csrc/bpr_ldsbin.inc ldsbin_launch_range restated
+        for a whole epoch and a 16-wave workgroup"""
+        t, bins = self.lds_tables, self.plan["bins"]
+        key = int(orc.lib().oracle_ldsbin_key(int(self.seed), 0))
+        _, cold, off = orc.ldsbin_deal_key(key, bins, self.ni, t["n_hot"], orc.ldsbin_n_strata(self.ni, bins, 16), 32,
+                                           t["rank_item"], t["cptr"], t["n_hot_inter"])
+        draws = cold.astype(np.int64) + np.diff(off.astype(np.int64))
+        tile_w = np.where(draws < 8 * 16 * 64, 32, 64)
+        return draws, tile_w, -(-draws // tile_w)
+
+    def exch_segments(self, n_ex):
+        """per triplet: how many exchange boundaries of its bin lie before it.  Boundary e < n_ex - 1 sits at the bin's draw
+        (e + 1) (n_tiles // n_ex) tile_w, the last one (every one of a bin with fewer tiles than exchanges) at the end of the
+        launch.  The restatement names a bin's triplets in draw order but not their draws: the m-th triplet stands for draw
+        m, so a boundary sits late by the bin's skipped draws before it (a few in a thousand)."""
+        _, tile_w, tiles = self.exch_tiles()
+        per = (tiles // n_ex) * tile_w
+        first = np.flatnonzero(np.r_[True, self.bin[1:] != self.bin[:-1]])
+        assert len(np.unique(self.bin[first])) == len(first), "the restatement goes bin by bin"
+        m = np.arange(len(self.bin)) - np.repeat(first, np.diff(np.r_[first, len(self.bin)]))
+        p = per[self.bin]
+        return np.where(p > 0, np.minimum(m // np.maximum(p, 1), n_ex - 1), 0)
+
     def triplets_of(self, table, row):
         u, i, j = self.trip
         return np.flatnonzero(u == row if table == "U" else (i == row) | (j == row))
@@ -532,14 +627,20 @@ def check_a(c, got):
     return worst
 
 
-def tolerance_b(c, tab, coeff=None):
-    """per-row tolerance of launch B for one table: C x path + touches x ulp(max |row|) / 2 x sqrt(k)"""
+def tolerance_b(c, tab, coeff=None, extra=0, reach=False):
+    """per-row tolerance of launch B for one table: C x path + touches x ulp(max |row|) / 2 x sqrt(k), max |row| taken from the
+    row's start and its Jacobi end.  extra: further float32 roundings of the row to add to `touches` in the floor term (the
+    resident exchange: one per exchange).  reach: max |row| = max |start| + path instead, which bounds the row at EVERY moment
+    of the launch — for the identities that have the floor term alone (coeff = 0): a bias of 5e-6 that steps of 1e-4 carry
+    away and back is rounded at the ulp of 1e-4 on the way, which C x path covers in the rules and nothing in an identity"""
     coeff = C[c.name] if coeff is None else coeff
     j = c.jac[tab]
     start = c.tables["UVB".index(tab)].astype(np.float64).reshape(len(j["touches"]), -1)
     top = np.maximum(np.abs(start), np.abs(start + j["sum"].reshape(start.shape))).max(axis=1)
+    if reach:
+        top = np.abs(start).max(axis=1) + j["path"]
     half_ulp = np.spacing(top.astype(np.float32)).astype(np.float64) / 2
-    return coeff * j["path"] + j["touches"] * half_ulp * np.sqrt(start.shape[1])
+    return coeff * j["path"] + (j["touches"] + extra) * half_ulp * np.sqrt(start.shape[1])
 
 
 def check_b(c, got, coeff=None, other_rule=None):
@@ -636,3 +737,161 @@ def racy_visible(c, coeff=None):
         return np.zeros(0, bool)
     r, m = np.concatenate([a for a, _ in rows]), np.concatenate([b for _, b in rows])
     return path[r] / m > 2 * tol[r]
+
+
+# ---- the resident exchange: the table, and what the launch publishes ------------------------------------------------------------
+# `res` = what a launch left, as the device test reads it back (and the host model of tests/test_bpr_step_cpu.py returns it):
+# U [nu, k]; flat, base [nt k + nt] (the replicated item table [V | B] and its base, read BEFORE the driver's closing exchange);
+# signals [2 n_ex + 1] (arrivals | landed flags | error word); applied [nt]; red = exch_reduce(keeps, buckets).
+class ExchReducer:
+    """What the checks need of the keeps [n_ex][nt k + nt] and buckets [n_ex][nt k + 3 nt] of a launch, taken in exchange by
+    exchange where the buffers are (torch tensors on the device: float32; the float64 host model's arrays as they are), in
+    float64: ksum = sum_e keeps[e]; csum = sum_e (rule(buckets[e]) - keeps[e]), the corrections the launch and the flush apply
+    between them; all_zero; bucket_is_keep (buckets[e][:width] == keeps[e], or 2 keeps[e] with a twin, bit for bit); under
+    "sqrt" w_exact (wV[e][i] == ranks x (row i of keeps[e] has a non-zero), wB likewise), under "align" w_rel (largest |w -
+    ranks x sum d^2| / that, the sum in float64)."""
+
+    def __init__(self, c):
+        self.c, self.n, self.ksum, self.csum = c, 0, None, None
+        self.out = dict(all_zero=True, bucket_is_keep=True, w_exact=True, w_rel=0.0)
+
+    def add(self, keep, bucket):
+        import torch
+
+        c, out = self.c, self.out
+        K, Bk = torch.as_tensor(keep), torch.as_tensor(bucket)
+        nt, k = c.total_items, c.k
+        nk, width, ranks = nt * k, nt * k + nt, 2.0 if c.twin else 1.0
+        assert K.shape == (width,) and Bk.shape == (width + 2 * nt,) and K.dtype == Bk.dtype
+        if self.ksum is None:
+            self.ksum = torch.zeros(width, dtype=torch.float64, device=K.device)
+            self.csum = torch.zeros_like(self.ksum)
+        self.n += 1
+        S, wV, wB, Kd = Bk[:width].double(), Bk[width:width + nt], Bk[width + nt:], K.double()
+        self.ksum += Kd
+        out["all_zero"] &= not bool(K.any()) and not bool(Bk.any())
+        out["bucket_is_keep"] &= bool(torch.equal(Bk[:width], K * ranks))
+        dV, dB = Kd[:nk].view(nt, k), Kd[nk:]
+        if c.rule == "sqrt":
+            out["w_exact"] &= bool(torch.equal(wV.double(), ranks * (dV != 0).any(dim=1).double())) and bool(
+                torch.equal(wB.double(), ranks * (dB != 0).double()))
+            fV, fB = wV.double().clamp(min=1.0).rsqrt(), wB.double().clamp(min=1.0).rsqrt()
+        else:
+            for w, want in ((wV, ranks * (dV * dV).sum(dim=1)), (wB, ranks * dB * dB)):
+                out["w_exact"] &= bool((w[want == 0] == 0).all())
+                rel = ((w.double() - want).abs() / want)[want > 0]
+                out["w_rel"] = max(out["w_rel"], float(rel.max()) if rel.numel() else 0.0)
+            n2V, n2B = (S[:nk].view(nt, k) ** 2).sum(dim=1), S[nk:] ** 2
+            fV = torch.where(n2V > 0, (wV.double() / n2V).clamp(max=1.0), torch.ones_like(n2V))
+            fB = torch.where(n2B > 0, (wB.double() / n2B).clamp(max=1.0), torch.ones_like(n2B))
+        self.csum[:nk] += (S[:nk].view(nt, k) * fV[:, None]).reshape(-1) - Kd[:nk]
+        self.csum[nk:] += S[nk:] * fB - Kd[nk:]
+
+    def result(self):
+        assert self.n == self.c.n_ex
+        return dict(self.out, ksum=self.ksum.cpu().numpy(), csum=self.csum.cpu().numpy())
+
+
+def exch_reduce(c, keeps, buckets):
+    red = ExchReducer(c)
+    for e in range(c.n_ex):
+        red.add(keeps[e], buckets[e])
+    return red.result()
+
+
+def _exch_vb(c, flat):
+    nk = c.total_items * c.k
+    return flat[:nk].reshape(c.total_items, c.k), flat[nk:]
+
+
+def exch_tables(c, res, uncorrected=False):
+    """(U, V, B) of a launch; uncorrected: with the corrections the buffers name taken out again (float64 sum, one rounding)"""
+    flat = (res["flat"].astype(np.float64) - res["red"]["csum"]).astype(np.float32) if uncorrected else res["flat"]
+    return (res["U"],) + _exch_vb(c, flat)
+
+
+def check_exch_signals(c, res):
+    sig, n_ex = np.asarray(res["signals"]), c.n_ex
+    assert (sig[:n_ex] == c.plan["bins"]).all(), "%s: arrivals %s, bins %d" % (c.name, sig[:n_ex], c.plan["bins"])
+    assert (sig[n_ex:2 * n_ex] == 1).all() and sig[2 * n_ex] == 0, "%s: landed flags %s, error word %d" % (c.name, sig[n_ex:2 * n_ex], sig[2 * n_ex])
+    ap = np.asarray(res["applied"])
+    assert ((ap >= 0) & (ap <= n_ex)).all() and (ap[c.ni:] == 0).all(), "%s: the applied[] record" % c.name
+
+
+def check_exch_z(c, res):
+    """launch Z of a resident-exchange case beyond check_z: nothing published but exact zeros, the base is the table"""
+    check_exch_signals(c, res)
+    assert res["red"]["all_zero"], "%s: lr = 0 published a non-zero keep or bucket word" % c.name
+    assert np.array_equal(res["flat"], res["base"]), "%s: lr = 0 left table and base apart" % c.name
+
+
+def check_exch_a(c, res):
+    """launch A: check_a, unchanged — on the table less its corrections where they are not zero (twin, "sqrt": a clean row
+    holds (sqrt(2) - 1) of its own step on top, sooner or later)"""
+    check_exch_signals(c, res)
+    return check_a(c, exch_tables(c, res, uncorrected=c.twin and c.rule == "sqrt"))
+
+
+def _exch_rows(c, tab, got, want, coeff, what):
+    """per row of V (or element of B): |got - want| <= tolerance_b(coeff) with n_ex more roundings (coeff = 0: its floor term
+    alone, max |row| by its reach), Euclidean over the row; `want` None = the Jacobi sum, on the touched rows, and an exact zero
+    on the others.
+    Returns the largest error / tolerance."""
+    j = c.jac[tab]
+    tol = tolerance_b(c, tab, coeff, extra=c.n_ex, reach=want is not None)
+    if want is None:
+        quiet = np.flatnonzero((j["touches"] == 0) & (got != 0).reshape(len(tol), -1).any(axis=1))
+        assert len(quiet) == 0, "%s: %s of a row no triplet touches is not zero: %s" % (c.name, what, c.describe(tab, int(quiet[0])))
+        rows, want = np.flatnonzero(j["touches"] > 0), j["sum"]
+    else:
+        rows = np.arange(len(tol))
+    if len(rows) == 0:
+        return 0.0
+    err = np.linalg.norm((got[rows] - want[rows]).reshape(len(rows), -1), axis=1)
+    bad = np.flatnonzero(err > tol[rows])
+    assert len(bad) == 0, "launch B, %s off by %.3g > %.3g (path %.3g; %d such rows): %s" % (
+        what, err[bad[0]], tol[rows][bad[0]], j["path"][rows[bad[0]]], len(bad), c.describe(tab, int(rows[bad[0]])))
+    return float((err / tol[rows]).max()) if len(rows) else 0.0
+
+
+def check_exch_b(c, res, coeff=None, lock_timeouts=0):
+    """launch B of a resident-exchange case.  Returns the largest error / tolerance of the table rule (U, V, B), of the
+    published-delta rule (PV, PB) and of the floor-only identities (floor), and the rows left apart from their base (left)."""
+    check_exch_signals(c, res)
+    red = res["red"]
+    start = np.concatenate([c.tables[1].ravel(), c.tables[2]]).astype(np.float64)
+    flat, base = res["flat"].astype(np.float64), res["base"].astype(np.float64)
+    owed = flat - base
+    P = red["ksum"] + owed
+    accounting = c.twin and c.rule == "sqrt"
+    if accounting:
+        # whatever the timing: the table is its start, the rank's steps and the corrections; the base lacks what is still owed.
+        # U takes no correction, but its steps saw rows displaced by them: the same C as P
+        out = check_b(c, exch_tables(c, res), coeff, other_rule={tab: np.ones(c.total_items, bool) for tab in "VB"})
+        steps, published = flat - start - red["csum"], base - start - red["csum"]
+    else:
+        out = check_b(c, exch_tables(c, res), coeff)  # 1: one rank alone makes the exchange the identity
+        steps, published = flat - start, base - start
+    # 2: what the other ranks receive, and what the closing exchange still owes them
+    for tab, p in zip("VB", _exch_vb(c, P)):
+        out["P" + tab] = _exch_rows(c, tab, p, None, coeff, "the published delta")
+    # 3: only hot rows are stepped after their last publication
+    apart = np.flatnonzero((_exch_vb(c, owed)[0] != 0).any(axis=1) | (_exch_vb(c, owed)[1] != 0))
+    cold = np.setdiff1d(apart, c.hot_items)
+    assert len(cold) == 0 and len(apart) <= c.n_hot, "%s: %d rows differ from their base, %d of them cold (n_hot %d): %s" % (
+        c.name, len(apart), len(cold), c.n_hot, c.describe("V", int(cold[0])) if len(cold) else "")
+    out["left"] = len(apart)
+    # 4: the bucket of one rank is its keep (of two equal ranks: twice it), with the rule's weights
+    assert red["bucket_is_keep"], "%s: buckets[:, :width] != %s keeps" % (c.name, "2 x" if c.twin else "")
+    assert red["w_exact"], "%s: a weight word differs from what its keep row says" % c.name
+    w_tol = (c.k + 2) * 2.0 ** -24
+    assert red["w_rel"] <= w_tol, "%s: a weight is %.3g (relative) off the float64 sum of squares, tolerance %.3g" % (c.name, red["w_rel"], w_tol)
+    out["w_rel"] = red["w_rel"] / w_tol
+    # 5 / the accounting: no delta published twice or never, no correction applied twice or never — within the roundings
+    worst = 0.0
+    for tab, s, p, pub, ks in zip("VB", _exch_vb(c, steps), _exch_vb(c, P), _exch_vb(c, published), _exch_vb(c, red["ksum"])):
+        worst = max(worst, _exch_rows(c, tab, pub, ks, 0.0, "base - start%s - sum of keeps" % (" - corrections" if accounting else "")))
+        worst = max(worst, _exch_rows(c, tab, s, p, 0.0, "table - start%s - P" % (" - corrections" if accounting else "")))
+    out["floor"] = worst
+    assert lock_timeouts == 0, "%s: %d lock time-outs" % (c.name, lock_timeouts)
+    return out

@@ -82,7 +82,8 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
     z05, z95 = np.quantile(z, [0.05, 0.95])
     assert z05 <= 0.25 and z95 >= 0.75, (z05, z95)
     ambiguous = int((np.abs(c.x) < c.x_bound).sum())
-    assert ambiguous <= max(2, n_trip // 10_000), "the float32 score bound decides nearly every sign: %d of %d ambiguous" % (ambiguous, n_trip)
+    # (a resident-exchange launch is a whole epoch at k up to 256, and the bound grows with k: one triplet in 2 000)
+    assert ambiguous <= (n_trip // 2_000 if c.exch else max(2, n_trip // 10_000)), "the float32 score bound decides nearly every sign: %d of %d ambiguous" % (ambiguous, n_trip)
     # launch A: enough clean triplets (LDS bins: enough of them with a hot positive)
     n_clean = int(c.clean.sum())
     n_hot_clean = int((c.clean & c.hot).sum()) if c.hot is not None else None
@@ -95,6 +96,8 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
         else:  # popularity negatives: every negative is a positive of the launch too, launch B carries the case
             assert c.kind == "pop" and c.neg_pop and not c.clean_share
             assert (np.bincount(c.indices, minlength=c.ni)[c.trip[2]] > 0).all(), "a negative is the item of an interaction"
+    elif c.exch:  # a whole epoch: next to no triplet is clean, launch B carries the family (its conditions: _exch_case_is_fair)
+        assert not c.clean_share and c.n == c.nnz and c.s_begin == 0
     elif c.clean_share:
         assert n_clean >= 300 and 3 * n_clean >= n_trip, (n_clean, n_trip)
         if c.form == "ldsbin":
@@ -110,7 +113,9 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
     t32 = _t32_measured(c)
     assert t32 <= bc.T_CLEAN / 4, (t32, bc.T_CLEAN)
     # C[case]: 4 x measured, rounded up to one significant digit
-    cm = _c_measured(c)
+    # (the "sqrt" twin: its steps are taken on rows displaced by (sqrt(2) - 1) of the rank's own earlier deltas — the share of
+    # three host runs of the protocol instead)
+    cm = _c_twin_measured(c) if c.exch and c.twin and c.rule == "sqrt" else _c_measured(c)
     assert 4 * cm <= bc.C[name] <= bc.round_up_1sig(4 * cm * 1.05), (name, cm, bc.round_up_1sig(4 * cm))
     # launch B: one lost or doubled update shows on at least half of the touched rows
     vis = {tab: bc.visibility(c, tab) for tab in ("UVB" if c.use_bias else "UV")}
@@ -121,7 +126,9 @@ def test_case_is_a_fair_test_and_its_tolerances_follow_their_rules(oracle, name)
               c.touches["U"].max(), tv.max(), t32, cm, bc.round_up_1sig(4 * cm),
               ", ".join("%s %.2f" % kv for kv in vis.items())))
     if not c.only_b:  # (the wide-tile case alone may fall below: its comment says why)
-        assert min(vis.values()) >= 0.5, vis
+        assert min(vis.values()) >= (0.8 if c.exch else 0.5), vis
+    if c.exch:
+        _exch_case_is_fair(c, n_trip)
     if c.form == "strata":
         _strata_case_is_fair(c, n_trip)
     if c.form == "owned":
@@ -490,3 +497,271 @@ def test_the_racy_rule_rejects_a_wrong_racy_row(oracle, name, mutant):
         name, mutant, visible.mean(), len(rows), rejected, (~r["ok"]).mean()))
     assert visible.mean() >= 0.5 and rejected >= 0.9
     assert _fails(bc.check_b_strata, c, _as_device((U, V, B)))
+
+
+# ---- the resident exchange: a float64 host model of the protocol, the cases' conditions, and the protocol's own ways of being wrong ----
+EXCH_FAULTS = ("step_left_out_of_the_published_delta", "delta_published_by_two_exchanges", "row_never_published",
+               "correction_applied_by_the_launch_and_by_the_flush", "correction_never_applied",
+               "hot_delta_and_base_from_two_reads", "keeps_written_with_the_bucket_value", "weight_left_at_zero")
+_TWIN_ONLY = EXCH_FAULTS[3:5] + EXCH_FAULTS[6:7]  # (without a twin every correction is an exact zero and bucket == keep)
+
+
+def _exch_victim(c, seg):
+    """a cold item row that ONE triplet touches, before the first boundary of its bin, on which one update shows: (row, the
+    triplet's float64 delta of launch B for [row | bias])"""
+    u, i, j = c.trip
+    vis = c.jac["V"]["path"] > 2 * bc.tolerance_b(c, "V", extra=c.n_ex)
+    hot = np.zeros(c.total_items, bool)
+    hot[c.hot_items] = True
+    t = int(np.flatnonzero((seg == 0) & (c.touches["V"][i] == 1) & ~hot[i] & vis[i])[0])
+    _, _, _, dVi, _, dBi, _ = step.deltas(tuple(a[t:t + 1] for a in c.trip), *c.tables, bc.LR_B, bc.REG, c.use_bias)
+    return int(i[t]), np.r_[dVi[0], dBi[0]]
+
+
+def exch_host_launch(c, lr, n_ex, rule, twin, lag, fault=None):
+    """The resident exchange of csrc/bpr_ldsbin.inc and cornac_amd/dist.py in float64 numpy, all bins in step: the triplets
+    in the restatement's order, segment by segment (Case.exch_segments: boundary e of a bin at its draw (e + 1) (n_tiles //
+    n_ex) tile_w, the last at the end); at boundary e every row publishes d = row - base into bucket e (twice it with a
+    twin) and keep e, with the rule's weights, and base = row; an exchange is applied `lag` boundaries after its
+    publication (row += c, base += c, c = rule(S) - keep), the rest by the flush.  The hot rows publish their last delta
+    BEFORE the last fiftieth of the launch's triplets (their owner bin has finished, other bins step them still): what
+    they take afterwards is table - base.  One rank alone has S = d and a weight that makes the factor 1: c is an exact zero
+    and is not computed.  Returns `res` as the device test reads it back — U, table and base rounded to float32; the keeps
+    and buckets go to the reducer in float64 as they are (a float32 keep is the exact difference of two float32 rows on the
+    device, which a rounded float64 difference is not) — and, under "f64", the float64 U, table and P.  fault: one of
+    EXCH_FAULTS, on the row of _exch_victim (the hot fault: on the first hot row)."""
+    from oracle import oracle as orc
+
+    assert (n_ex, rule, twin) == (c.n_ex, c.rule, c.twin)  # (bc.ExchReducer reads them from the case)
+    nt, k = c.total_items, c.k
+    nk, width, ranks = nt * k, nt * k + nt, 2.0 if twin else 1.0
+    reg = bc.REG if lr else 0.0
+    U = c.tables[0].astype(np.float64)
+    flat = np.concatenate([c.tables[1].ravel(), c.tables[2]]).astype(np.float64)
+    V, B = flat[:nk].reshape(nt, k), flat[nk:]  # (views: the steps go into `flat`)
+    base = flat.copy()
+    red, pending, ksum = bc.ExchReducer(c), {}, np.zeros(width)
+    seg = c.exch_segments(n_ex)
+    hot_els = np.concatenate([(c.hot_items[:, None] * k + np.arange(k)[None, :]).ravel(), nk + c.hot_items]).astype(np.int64)
+    victim = delta = els = None
+    if fault is not None and fault != "hot_delta_and_base_from_two_reads":
+        victim, delta = _exch_victim(c, seg)
+    elif fault is not None:
+        victim = int(c.hot_items[0])
+        t = c.triplets_of("V", victim)[-1:]
+        _, _, _, dVi, dVj, dBi, dBj = step.deltas(tuple(a[t] for a in c.trip), *c.tables, bc.LR_B, bc.REG, c.use_bias)
+        delta = np.r_[dVi[0], dBi[0]] if c.trip[1][t[0]] == victim else np.r_[dVj[0], dBj[0]]
+    if fault is not None:
+        assert lr == bc.LR_B, "the protocol's faults are launch B's to find"
+        els = np.r_[victim * k:(victim + 1) * k, nk + victim]
+    published_once = False
+
+    def correction(e):
+        K, Bk = pending.pop(e)
+        S, wV, wB = Bk[:width], Bk[width:width + nt], Bk[width + nt:]
+        if rule == "sqrt":
+            fV, fB = 1.0 / np.sqrt(np.maximum(wV, 1.0)), 1.0 / np.sqrt(np.maximum(wB, 1.0))
+        else:
+            n2V, n2B = (S[:nk].reshape(nt, k) ** 2).sum(axis=1), S[nk:] ** 2
+            fV = np.where(n2V > 0, np.minimum(1.0, wV / np.where(n2V > 0, n2V, 1.0)), 1.0)
+            fB = np.where(n2B > 0, np.minimum(1.0, wB / np.where(n2B > 0, n2B, 1.0)), 1.0)
+        cc = np.empty(width)
+        cc[:nk] = (S[:nk].reshape(nt, k) * fV[:, None]).ravel() - K[:nk]
+        cc[nk:] = S[nk:] * fB - K[nk:]
+        return cc
+
+    def apply(e):
+        if not twin:
+            return
+        cc = correction(e)
+        if fault == "correction_never_applied" and e == 0:
+            cc[els] = 0.0
+        if fault == "correction_applied_by_the_launch_and_by_the_flush" and e == 0:
+            cc[els] *= 2.0
+        flat[:] += cc
+        base[:] += cc
+
+    def publish(e, hot_snapshot=None):
+        nonlocal published_once
+        cur = flat.copy()
+        if hot_snapshot is not None:
+            cur[hot_els] = hot_snapshot
+        d = cur - base
+        hold = None  # elements whose base does not move to `cur`
+        if fault == "row_never_published":
+            d[els], hold = 0.0, els
+        elif victim is not None and not published_once and d[els].any():
+            published_once = True
+            if fault == "step_left_out_of_the_published_delta":
+                d[els] -= delta
+            elif fault == "delta_published_by_two_exchanges":
+                hold = els
+        Bk = np.empty(width + 2 * nt)
+        Bk[:width] = ranks * d
+        dV, dB = d[:nk].reshape(nt, k), d[nk:]
+        if rule == "sqrt":
+            Bk[width:width + nt], Bk[width + nt:] = ranks * (dV != 0).any(axis=1), ranks * (dB != 0)
+        else:
+            Bk[width:width + nt], Bk[width + nt:] = ranks * (dV * dV).sum(axis=1), ranks * dB * dB
+        if fault == "weight_left_at_zero" and d[els].any():
+            Bk[width + victim] = 0.0
+        if fault == "keeps_written_with_the_bucket_value":
+            d = Bk[:width].copy()
+        red.add(d, Bk)
+        ksum[:] += d
+        if twin:
+            pending[e] = (d, Bk)
+        kept = base[hold].copy() if hold is not None else None
+        base[:] = cur
+        if hold is not None:
+            base[hold] = kept
+        if fault == "hot_delta_and_base_from_two_reads" and hot_snapshot is not None:
+            base[els] += delta  # the base was read a step after the delta
+
+    applied = 0
+    for q in range(n_ex):
+        ids = np.flatnonzero(seg == q)
+        snap = None
+        if q == n_ex - 1:
+            cut = len(ids) - len(ids) // 50
+            orc.bpr_apply_seq_f64(c.trip, ids[:cut], U, V, B, lr, reg, c.use_bias)
+            snap, ids = flat[hot_els].copy(), ids[cut:]
+        orc.bpr_apply_seq_f64(c.trip, ids, U, V, B, lr, reg, c.use_bias)
+        publish(q, snap)
+        while applied + lag <= q:
+            apply(applied)
+            applied += 1
+    in_launch = applied
+    while applied < n_ex:  # the flush
+        apply(applied)
+        applied += 1
+    signals = np.r_[np.full(n_ex, c.plan["bins"]), np.ones(n_ex, np.int64), 0]
+    record = np.zeros(nt, np.int64)
+    record[:c.ni] = in_launch
+    return dict(U=U.astype(np.float32), flat=flat.astype(np.float32), base=base.astype(np.float32), signals=signals, applied=record,
+                red=red.result(), f64=dict(U=U, flat=flat, P=ksum + (flat - base)))
+
+
+def _c_twin_measured(c):
+    """largest |P - jacobi| / path (U: |table - start - jacobi| / path) over the touched rows, float64, over three host runs of
+    the protocol that apply an exchange 0, 1 and n_ex boundaries after its publication"""
+    worst = 0.0
+    for lag in (0, 1, c.n_ex):
+        f = exch_host_launch(c, bc.LR_B, c.n_ex, c.rule, c.twin, lag)["f64"]
+        moved = {"U": f["U"] - c.tables[0].astype(np.float64)}
+        moved["V"], moved["B"] = bc._exch_vb(c, f["P"])
+        for tab in "UVB":
+            j = c.jac[tab]
+            rows = np.flatnonzero(j["touches"] > 0)
+            dev = np.linalg.norm((moved[tab][rows] - j["sum"][rows]).reshape(len(rows), -1), axis=1)
+            worst = max(worst, float((dev / j["path"][rows]).max()))
+    return worst
+
+
+_EXCH_FACTS = {}  # per exchange case, filled as the cases go by: (neg_pop, triplets with a hot positive, skipped draws)
+
+
+def _exch_facts(name):
+    if name not in _EXCH_FACTS:
+        c = bc.case(name)
+        _EXCH_FACTS[name] = (c.neg_pop, int(c.hot.sum()), c.skipped)
+    return _EXCH_FACTS[name]
+
+
+def _exch_case_is_fair(c, n_trip):
+    """the conditions of a resident-exchange case from the restatement alone, and the unmutated host model, rounded to
+    float32, through every check of the device test"""
+    _EXCH_FACTS[c.name] = (c.neg_pop, int(c.hot.sum()), c.skipped)
+    draws, tile_w, tiles = c.exch_tiles()
+    per = tiles // c.n_ex
+    tv = c.touches["V"]
+    print("\n%s: plan %d bins x %d rows, n_ex %d, rule %s%s; %d..%d tiles of %d draws per bin, %d..%d between two boundaries; %d triplets, "
+          "%d skipped, %d with a hot positive (n_hot %d); mean touches of a touched V row %.1f" % (
+              c.name, c.plan["bins"], c.plan["cap"], c.n_ex, c.rule, ", twin" if c.twin else "", tiles.min(), tiles.max(), tile_w.max(),
+              per.min(), per.max(), n_trip, c.skipped, int(c.hot.sum()), c.n_hot, tv[tv > 0].mean()))
+    assert c.n_ex * (c.total_items * c.k + 3 * c.total_items) <= 2.5e8, "buckets and keeps near 1 GB each at the most"
+    assert (tile_w == 32).all()
+    bins = {"exch_k40": 256, "exch_nobias_k64": 256, "exch_partial_k64": 256, "exch_one_k64": 256, "exch_ex32_k64": 256,
+            "exch_twin_sqrt_k64": 256}.get(c.name, 1024)
+    assert c.plan["bins"] == bins and not c.plan["passing"], c.plan
+    if c.name == "exch_partial_k64":
+        assert c.ni % bins == 13 and c.plan["cap"] == 257
+    if c.name == "exch_one_k64":
+        assert c.n_ex == 1
+    elif c.name == "exch_ex32_k64":  # ex_per = 1: one part per boundary, a boundary on every tile
+        assert c.n_ex == 32 and (per == 1).all(), (per.min(), per.max())
+    elif c.name == "exch_short_k64":  # ex_per = 0: every boundary at the end of the launch
+        assert (per == 0).all() and tiles.min() >= 1, (tiles.min(), tiles.max())
+    else:
+        assert c.n_ex in (4, 8) and per.min() >= 2
+    coeff = bc.C[c.name]
+    z = exch_host_launch(c, 0.0, c.n_ex, c.rule, c.twin, 1)
+    bc.check_z(c, bc.exch_tables(c, z), int((c.x > 0).sum()), c.skipped)
+    bc.check_exch_z(c, z)
+    a = bc.check_exch_a(c, exch_host_launch(c, bc.LR_A, c.n_ex, c.rule, c.twin, 1))
+    for lag in ((0, 1, c.n_ex) if c.twin and c.rule == "sqrt" else (1,)):  # (a correction that is an exact zero has no timing)
+        b = bc.check_exch_b(c, exch_host_launch(c, bc.LR_B, c.n_ex, c.rule, c.twin, lag), coeff)
+        print("%s, host model, lag %d: A %s; B error / tolerance: table U %.3g V %.3g B %.3g, published deltas V %.3g B %.3g, "
+              "identities / floor %.3g, weights %.3g; %d rows apart from their base" % (
+                  c.name, lag, {t: "%.3g" % v for t, v in a.items()}, b["U"], b["V"], b["B"], b["PV"], b["PB"], b["floor"], b["w_rel"], b["left"]))
+        if c.hot.sum() >= 1000:
+            assert b["left"] > 0, "hot rows stepped after their last publication: table - base is part of P"
+
+
+def test_the_exch_cases_hold_hot_rows_and_a_skipped_draw(oracle):
+    facts = {name: _exch_facts(name) for name in bc.EXCH_NAMES}
+    print("\nresident-exchange cases, (popularity negatives, triplets with a hot positive, skipped draws): %s" % facts)
+    assert max(h for pop, h, _ in facts.values() if not pop) >= 1000 and max(h for pop, h, _ in facts.values() if pop) >= 1000
+    assert sum(s for _, _, s in facts.values()) >= 1
+
+
+@pytest.mark.parametrize("name,fault", [(name, fault) for name in ("exch_k64", "exch_twin_sqrt_k64") for fault in EXCH_FAULTS
+                                        if name == "exch_twin_sqrt_k64" or fault not in _TWIN_ONLY])
+def test_checks_reject_a_wrong_exchange_protocol(oracle, name, fault):
+    c = bc.case(name)
+    rejected = []
+    for lag in (0, 1, c.n_ex) if c.twin else (1,):
+        try:
+            bc.check_exch_b(c, exch_host_launch(c, bc.LR_B, c.n_ex, c.rule, c.twin, lag, fault=fault))
+            rejected.append(None)
+        except AssertionError as err:
+            rejected.append(str(err).split(":")[0][:90])
+    print("\n%s, %s: rejected by %s" % (c.name, fault, rejected))
+    assert all(rejected), (fault, rejected)
+
+
+@pytest.mark.parametrize("mutant", MUTANTS)
+def test_checks_reject_a_wrong_update_in_an_exchange_launch(oracle, mutant):
+    """the nine wrong updates on exch_k64: every triplet's (wrong) deltas from the start tables, as _strata_host_launch sums
+    them, everything published by the last exchange"""
+    c = bc.case("exch_k64")
+    nt, k, n = c.total_items, c.k, len(c.trip[0])
+    out = {}
+    for launch, lr in (("A", bc.LR_A), ("B", bc.LR_B)):
+        u, i, j = c.trip
+        _, _, dU, dVi, dVj, dBi, dBj = step.deltas(c.trip, *c.tables, lr, bc.REG, c.use_bias, fault=mutant if mutant in step.FAULTS else None)
+        w = np.ones(2 * n)
+        if mutant.startswith("one_update"):
+            row = int(np.flatnonzero(c.touches["V"] == 3)[0])
+            t = int(c.triplets_of("V", row)[-1])
+            w[t if i[t] == row else n + t] = 0.0 if mutant == "one_update_lost" else 2.0
+        U, V, B = (np.array(t, np.float64) for t in c.tables)
+        np.add.at(U, u, dU)
+        np.add.at(V, i, dVi * w[:n, None])
+        np.add.at(V, j, dVj * w[n:, None])
+        np.add.at(B, i, dBi * w[:n])
+        np.add.at(B, j, dBj * w[n:])
+        if mutant == "row_written_to_the_wrong_item":
+            a, b = i[np.flatnonzero(c.touches["V"][i] == 1)[:2]]
+            V[[a, b]] = V[[b, a]]
+        flat = np.concatenate([V.ravel(), B]).astype(np.float32)
+        keeps, buckets = np.zeros((c.n_ex, len(flat)), np.float32), np.zeros((c.n_ex, len(flat) + 2 * nt), np.float32)
+        keeps[-1] = (flat.astype(np.float64) - np.concatenate([c.tables[1].ravel(), c.tables[2]])).astype(np.float32)
+        buckets[-1, :len(flat)] = keeps[-1]
+        buckets[-1, len(flat):len(flat) + nt] = (keeps[-1, :nt * k].reshape(nt, k) != 0).any(axis=1)
+        buckets[-1, len(flat) + nt:] = keeps[-1, nt * k:] != 0
+        res = dict(U=U.astype(np.float32), flat=flat, base=flat.copy(), applied=np.zeros(nt, np.int64),
+                   signals=np.r_[np.full(c.n_ex, c.plan["bins"]), np.ones(c.n_ex, np.int64), 0], red=bc.exch_reduce(c, keeps, buckets))
+        out[launch] = _fails(bc.check_exch_a if launch == "A" else bc.check_exch_b, c, res)
+    print("\nexch_k64, %s: rejected by %s" % (mutant, " and ".join(key for key, v in out.items() if v) or "NOTHING"))
+    assert out["A"] or out["B"], mutant

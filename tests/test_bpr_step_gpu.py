@@ -3,7 +3,8 @@ dispatchers return runs one short launch three times (tests/bpr_step_cases.py: Z
 clean triplets, B at lr = 2^-12 on every touched row), and the triplets of that launch are known beforehand from the CPU
 restatements of the samplers.  tests/test_bpr_step_cpu.py proves the cases fair and the checks sharp.  The conveyor's
 launches (cornac_hip_bpr_conveyor_enqueue: the rows in block buffers) run under the same three rules in a test of their own,
-and so do the XCD-strata form's phases, whose launch B holds the cold item rows that two waves touch under a rule of their own."""
+and so do the XCD-strata form's phases, whose launch B holds the cold item rows that two waves touch under a rule of their own,
+and the resident exchange's whole epochs, whose launch B also holds what the launch publishes for the other ranks."""
 import numpy as np
 import pytest
 
@@ -26,7 +27,7 @@ def _launch(tr, c, lr):
     return tr.get_factors(), correct, skipped
 
 
-@pytest.mark.parametrize("name", [name for name in bc.NAMES if name not in bc.CONVEYOR_NAMES + bc.STRATA_NAMES])
+@pytest.mark.parametrize("name", [name for name in bc.NAMES if name not in bc.CONVEYOR_NAMES + bc.STRATA_NAMES + bc.EXCH_NAMES])
 def test_hogwild_launch_matches_the_float64_step(oracle, name):
     cus = _lib.device_info(0)["compute_units"]
     c = bc.case(name, cus)
@@ -197,6 +198,83 @@ def test_conveyor_launch_matches_the_float64_step(oracle, name):
           "error U %.3g V %.3g B %.3g (T_CLEAN %.3g); B error / tolerance U %.3g V %.3g B %.3g (C %.3g)" % (
               name, got[0], got[1], got[2], list(c.blocks), len(c.trip[0]), c.skipped, z["correct"], z["lo"], z["hi"], a["U"], a["V"],
               a["B"], bc.T_CLEAN, b["U"], b["V"], b["B"], bc.C[name]))
+
+
+def _exchange_launch(sh, tr, c, lr):
+    """one resident-exchange epoch of the case from its start tables, through the production driver: `res` as
+    bpr_step_cases.check_exch_* take it (table and base read BEFORE finish(), whose closing exchange makes base = table on a
+    rank without a process group), with the launch's counters"""
+    import torch
+
+    tr.set_factors(c.tables[0], None, None)
+    tr.seed_hogwild(c.seed)
+    sh.load_items(c.tables[1], c.tables[2])  # (base = table)
+    if sh._resident is not None:  # what the launch before left in the buffers says nothing about this one
+        with sh._on_stream():
+            for key in ("buckets", "keeps", "applied"):
+                sh._resident[key].zero_()
+        sh.stream.synchronize()
+    sh.run_epoch(c.nnz, c.n_ex, lr, bc.REG if lr else 0.0, c.use_bias, c.neg_population, c.flags, resident=True)
+    sh.stream.synchronize()
+    st = sh._resident
+    st["comm"].synchronize()
+    res = dict(flat=sh.table.flat.cpu().numpy(), base=sh.table.base.cpu().numpy(), signals=st["signals"].cpu().numpy(),
+               applied=st["applied"].cpu().numpy(), red=bc.exch_reduce(c, st["keeps"], st["buckets"]))
+    torch.cuda.synchronize()
+    res["correct"], res["skipped"] = sh.finish()
+    res["U"] = tr.get_user_factors()
+    assert np.array_equal(sh.table.flat.cpu().numpy(), res["flat"]) and np.array_equal(sh.table.base.cpu().numpy(), res["flat"]), (
+        "%s: one rank's closing exchange is the identity and leaves base = table" % c.name)
+    return res
+
+
+@pytest.mark.parametrize("name", bc.EXCH_NAMES)
+def test_resident_exchange_epoch_matches_the_float64_step(oracle, name):
+    """The resident exchange (csrc/bpr_ldsbin.inc, EXCH instantiations) through cornac_amd.dist.ShardedBprTrainer on ONE rank
+    without a process group: a whole epoch per launch, Z, A and B, and in launch B what the launch publishes (keeps, buckets,
+    base) beside the table — bpr_step_cases.check_exch_b.  A twin case plays a second rank with the same deltas on the
+    communication stream."""
+    import torch
+
+    from cornac_amd.dist import ShardedBprTrainer
+
+    cus = _lib.device_info(0)["compute_units"]
+    c = bc.case(name, cus)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    tr = _lib.BprTrainer(c.indptr, c.indices, c.nu, c.ni, c.nu, c.total_items, c.k)
+    try:
+        tr.ldsbin_config(min_candidates=c.min_candidates, max_rounds=c.max_rounds)
+        tr.seed_hogwild(c.seed)
+        st = tr.ldsbin_stats()
+        assert (st["bins"], st["rows_per_bin"], st["block_threads"]) == (c.plan["bins"], c.plan["cap"], 1024), (st, c.plan)
+        sh = ShardedBprTrainer(tr, c.total_items, c.k, dev, sync_every=c.nnz, rule=c.rule)
+        sh.load_items(c.tables[1], c.tables[2])
+        assert sh.resident_bins(c.neg_population, c.flags) == c.plan["bins"]
+        if c.twin:
+            sh.resident_bucket_hook = lambda e, b: b.mul_(2.0)
+        rz = _exchange_launch(sh, tr, c, 0.0)
+        assert tr.ldsbin_stats()["n_hot"] == c.n_hot, "%s: n_hot %d, restatement %d" % (name, tr.ldsbin_stats()["n_hot"], c.n_hot)
+        z = bc.check_z(c, bc.exch_tables(c, rz), rz["correct"], rz["skipped"])
+        bc.check_exch_z(c, rz)
+        a = bc.check_exch_a(c, _exchange_launch(sh, tr, c, bc.LR_A))
+        rb = _exchange_launch(sh, tr, c, bc.LR_B)
+        lock_timeouts = tr.ldsbin_stats()["lock_timeouts"]
+        assert sh.table.exchanges.get("resident") == 3 * c.n_ex, sh.table.exchanges
+    finally:
+        tr.close()
+    acc = c.twin and c.rule == "sqrt"
+    apart_v, apart_b = bc._exch_vb(c, rb["flat"] != rb["base"])
+    print("\n%s: %d bins x %d rows, n_ex %d, rule %s%s; %d triplets (%d skipped), correct %d in [%d, %d]; A clean-row error U %.3g V %.3g "
+          "B %.3g (T_CLEAN %.3g); B: applied in the launch %d..%d of %d, %d rows apart from their base (n_hot %d), largest |sum c| %.3g" % (
+              name, c.plan["bins"], c.plan["cap"], c.n_ex, c.rule, ", twin" if c.twin else "", len(c.trip[0]), c.skipped, z["correct"],
+              z["lo"], z["hi"], a["U"], a["V"], a["B"], bc.T_CLEAN, rb["applied"][:c.ni].min(), rb["applied"][:c.ni].max(), c.n_ex,
+              int((apart_v.any(axis=1) | apart_b).sum()), c.n_hot, np.abs(rb["red"]["csum"]).max()))
+    b = bc.check_exch_b(c, rb, lock_timeouts=lock_timeouts)
+    print("%s: B error / tolerance: table rule U %.3g%s, published-delta rule V %.3g B %.3g (C %.3g); %s / floor %.3g; "
+          "weights / tolerance %.3g" % (
+              name, b["U"], "" if acc else " V %.3g B %.3g" % (b["V"], b["B"]), b["PV"], b["PB"], bc.C[name],
+              "twin accounting residual" if acc else "base - start - sum of keeps", b["floor"], b["w_rel"]))
 
 
 def test_conveyor_setup_refuses_k_above_256():
