@@ -13,16 +13,16 @@
 //   backward  one workgroup per row: the partials summed in ascending range order, then the row's held entries in ascending
 //             order, each adding f(1, p) - f(0, p) (all three likelihoods are affine in a binary x); then back through
 //             z, s = sigmoid, mu and the KL terms to ga1
-//   small Adam, W1 Adam   as vaecf.hip: one thread per entry; W1's finds the batch's holders of a column by bisection in
-//             the other orientation's index list; columns nobody of the batch holds get g = 0 and still decay and move
+//   small Adam, W1 Adam   as vaecf.hip: one thread per entry; W1's is vae_device.h's kernel, which finds the batch's holders
+//             of a column by bisection in the other orientation's index list; columns nobody of the batch holds get g = 0
+//             and still decay and move
 //   encode    again with the updated tables and the second noise plane: z and mu go to the side's factor tables
 // No float atomics; every sum has one fixed order, so the same inputs give the same bits.
 //
 // The dense pass is register-tiled vector FMA (64 x 64 logit tiles, 4 x 4 per thread; then 64 x 16 gradient tiles, 4 per
 // thread and 16-column chunk): f32-input MFMA has vector FMA's peak on this part, and the chains stay ascending this way.
-#include "sparse_model.h"
 #include "rng.h"
-#include "vae_device.h"
+#include "vae_host.h"
 
 namespace chip {
 namespace {
@@ -68,8 +68,7 @@ __global__ void bv_noise_kernel(float *eps, int64_t n, int k, int64_t batch_size
     uint32_t o[4];
     philox4x32_10((uint32_t)r, (uint32_t)c, (uint32_t)t, ((uint32_t)((uint64_t)t >> 32) << 2) | ((uint32_t)draw << 1) | (uint32_t)side,
                   (uint32_t)seed, (uint32_t)(seed >> 32), o);
-    const float u1 = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    eps[e] = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+    eps[e] = normal(o[0], o[1]);
 }
 
 // ---- encode: one workgroup per row (bivae.py:103-109, 119-121) --------------------------------------------------------------------
@@ -322,25 +321,6 @@ __global__ void bv_small_adam_kernel(float *w, float *am, float *av, BvLayout L,
     vae_adam(w, am, av, at, g, ad);
 }
 
-// ---- Adam on W1 (one row per id n of the other side): the gradient of row n is the sum of ga1[b] over the batch's rows that
-// hold n, a range of n's ascending list in the other orientation, found by bisection (batches are consecutive id ranges) ------------
-__global__ void bv_w1_adam_kernel(float *w, float *am, float *av, BvLayout L, int64_t N, int h, int64_t r0, int64_t nb,
-                                  const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ col_idx,
-                                  const float *__restrict__ ga1, VaeAdam ad) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N * h) return;
-    const int64_t n = e / h, j = e % h;
-    int64_t lo = col_ptr[n], hi = col_ptr[n + 1];
-    const int64_t end = hi;
-    while (lo < hi) {   // the first of n's holders that is not below r0
-        const int64_t mid = (lo + hi) >> 1;
-        if (col_idx[mid] < r0) lo = mid + 1; else hi = mid;
-    }
-    float g = 0.f;
-    for (; lo < end && col_idx[lo] < r0 + nb; ++lo) g += ga1[((int64_t)col_idx[lo] - r0) * h + j];
-    vae_adam(w, am, av, L.W1 + e, g, ad);
-}
-
 // ---- scores: sigmoid(<mu_theta[u], mu_beta[i]>), one thread per entry; items == NULL: the rows of users[0 .. nb) --------------------
 __global__ void bv_score_kernel(const float *__restrict__ mu_theta, const float *__restrict__ mu_beta, const int32_t *__restrict__ users,
                                 const int32_t *__restrict__ items, int64_t nb, int64_t I, int k, float *out) {
@@ -382,7 +362,6 @@ struct cornac_hip_bivae : ModelHandle {
     }
 };
 
-static unsigned bv_grid(int64_t n) { return (unsigned)((n + kVaeBlock - 1) / kVaeBlock); }
 static int64_t bv_splits(int64_t N) { return (N + kBvRange - 1) / kBvRange; }
 
 static void bv_ensure(cornac_hip_bivae_t h, int64_t cap) {
@@ -453,23 +432,13 @@ static void bv_table(cornac_hip_bivae_t h, int q, BvSide **side, int64_t *off, i
 // host <-> device copies of the 12 tables of one kind (0 w, 1 m, 2 v), in the reference's shapes (fc0.weight is [h x N]
 // there, [N x h] here)
 static void bv_put(cornac_hip_bivae_t h, int kind, const float *const *tables) {
-    std::vector<std::vector<float>> keep;   // (alive until the synchronise)
     for (int q = 0; q < 12; ++q) {
         if (!tables[q]) continue;
         BvSide *d; int64_t off, rows, cols;
         bv_table(h, q, &d, &off, &rows, &cols);
         DevBuf<float> &buf = kind == 0 ? d->w : kind == 1 ? d->m : d->v;
-        const float *src = tables[q];
-        if (q % 6 == 0) {
-            keep.emplace_back((size_t)(rows * cols));
-            std::vector<float> &t = keep.back();
-            for (int64_t j = 0; j < rows; ++j)
-                for (int64_t i = 0; i < cols; ++i) t[(size_t)(i * rows + j)] = src[j * cols + i];
-            src = t.data();
-        }
-        HIP_CHECK(hipMemcpyAsync(buf.p + off, src, (size_t)(rows * cols) * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        put_table(h->stream, buf.p + off, tables[q], rows, cols, q % 6 == 0);
     }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
 static void bv_get(cornac_hip_bivae_t h, int kind, float *const *tables) {
@@ -478,18 +447,8 @@ static void bv_get(cornac_hip_bivae_t h, int kind, float *const *tables) {
         BvSide *d; int64_t off, rows, cols;
         bv_table(h, q, &d, &off, &rows, &cols);
         const DevBuf<float> &buf = kind == 0 ? d->w : kind == 1 ? d->m : d->v;
-        const size_t n = (size_t)(rows * cols);
-        if (q % 6 == 0) {
-            std::vector<float> t(n);
-            HIP_CHECK(hipMemcpyAsync(t.data(), buf.p + off, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            for (int64_t j = 0; j < rows; ++j)
-                for (int64_t i = 0; i < cols; ++i) tables[q][j * cols + i] = t[(size_t)(i * rows + j)];
-        } else {
-            HIP_CHECK(hipMemcpyAsync(tables[q], buf.p + off, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        }
+        get_table(h->stream, buf.p + off, tables[q], rows, cols, q % 6 == 0);
     }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
 int cornac_hip_bivae_set_params(cornac_hip_bivae_t h, const float *const *tables) {
@@ -587,8 +546,7 @@ static void bv_side_epoch(cornac_hip_bivae_t h, int s, int64_t batch_size, float
         const int64_t nb = std::min(batch_size, d.n - r0);
         const float inv_b = 1.0f / (float)nb;
         d.t += 1;
-        const double bc1 = 1.0 - std::pow(0.9, (double)d.t), bc2 = 1.0 - std::pow(0.999, (double)d.t);
-        const VaeAdam ad{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
+        const VaeAdam ad = adam_at(d.t, lr);
         bv_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(d.own->ptr.p, d.own->idx.p, r0, w, d.L, hh, k, h->act, eps1, h->h1.p,
                                                                    h->d1.p, h->mu.p, h->sd.p, h->z.p, h->kl.p, nullptr, nullptr);
         bv_dense(h, o.z.p, d.N, nb, inv_b);
@@ -596,9 +554,9 @@ static void bv_side_epoch(cornac_hip_bivae_t h, int s, int64_t batch_size, float
                                                                      h->part_ll.p, bv_splits(d.N), nb, w, d.L, hh, k, h->lik, beta, inv_b,
                                                                      eps1, h->d1.p, h->mu.p, h->sd.p, h->kl.p, h->gmu.p, h->gas.p,
                                                                      h->ga1.p, d.loss.p);
-        bv_small_adam_kernel<<<bv_grid(small), kVaeBlock, 0, h->stream>>>(w, am, av, d.L, hh, k, nb, h->gmu.p, h->gas.p, h->h1.p, h->ga1.p, ad);
-        bv_w1_adam_kernel<<<bv_grid(d.N * hh), kVaeBlock, 0, h->stream>>>(w, am, av, d.L, d.N, hh, r0, nb, d.other->ptr.p, d.other->idx.p,
-                                                                         h->ga1.p, ad);
+        bv_small_adam_kernel<<<grid(small), kVaeBlock, 0, h->stream>>>(w, am, av, d.L, hh, k, nb, h->gmu.p, h->gas.p, h->h1.p, h->ga1.p, ad);
+        vae_w1_adam_kernel<<<grid(d.N * hh), kVaeBlock, 0, h->stream>>>(w, am, av, d.L.W1, d.N, hh, r0, nb, d.other->ptr.p, d.other->idx.p,
+                                                                        h->ga1.p, ad);
         // bivae.py:220-223 / 250-252: the forward again, with the updated tables and fresh noise, into the factor tables
         bv_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(d.own->ptr.p, d.own->idx.p, r0, w, d.L, hh, k, h->act, eps2, nullptr,
                                                                    nullptr, nullptr, nullptr, nullptr, nullptr, d.z.p, d.mu.p);
@@ -619,7 +577,7 @@ int cornac_hip_bivae_fit_epoch(cornac_hip_bivae_t h, int64_t batch_size, float l
             BvSide &d = h->side[s];
             const float *eps = s == SIDE_ITEM ? eps_item : eps_user;
             if (eps) d.eps.upload(eps, d.eps.n, h->stream);
-            else bv_noise_kernel<<<bv_grid(2 * d.n * h->k), kVaeBlock, 0, h->stream>>>(d.eps.p, d.n, h->k, batch_size, d.t, s, seed);
+            else bv_noise_kernel<<<grid(2 * d.n * h->k), kVaeBlock, 0, h->stream>>>(d.eps.p, d.n, h->k, batch_size, d.t, s, seed);
             bv_side_epoch(h, s, batch_size, lr, beta_kl);
             HIP_CHECK(hipEventRecord(h->ev[s == SIDE_ITEM ? 1 : 2], h->stream));
         }
@@ -685,8 +643,8 @@ static void bv_predict(cornac_hip_bivae_t h, const int32_t *users, const int32_t
     if (h->out.n < need) alloc_named(h->out, need, "BiVAECF", "the scores");
     for_each_chunk("BiVAECF", *h, users, items, n, B, [&](int64_t b0, int64_t nb) {
         const int64_t cnt = items ? nb : nb * I;
-        bv_score_kernel<<<bv_grid(cnt), kVaeBlock, 0, h->stream>>>(h->side[SIDE_USER].mu.p, h->side[SIDE_ITEM].mu.p, h->user_ids.p,
-                                                                  items ? h->item_ids.p : nullptr, nb, I, h->k, h->out.p);
+        bv_score_kernel<<<grid(cnt), kVaeBlock, 0, h->stream>>>(h->side[SIDE_USER].mu.p, h->side[SIDE_ITEM].mu.p, h->user_ids.p,
+                                                                items ? h->item_ids.p : nullptr, nb, I, h->k, h->out.p);
         h->out.download(out + (items ? b0 : b0 * I), (size_t)cnt, h->stream);
     });
 }

@@ -7,8 +7,7 @@
 // gets the columns c .. c + VEC of row `row` of A H (d: the width of the hop).
 // The kernels sit in an unnamed namespace: every source that includes this header gets its own copies.
 #pragma once
-#include "sparse_model.h"
-#include "vae_device.h"
+#include "vae_host.h"
 
 namespace chip {
 namespace {
@@ -17,6 +16,7 @@ constexpr int kLgcnMaxD = 256, kLgcnMaxLayers = 8, kLgcnMaxStep = 16384;
 constexpr int kLgcnPiece = 512;      // edges of one piece of a long row
 constexpr int kLgcnAhead = 4;        // source rows in flight per lane group
 constexpr int kLgcnBlock = 256;
+static_assert(kLgcnBlock == kVaeBlock, "grid() counts workgroups of kVaeBlock by default");
 
 // the adjacency as the kernels see it
 struct LgcnGraph {
@@ -290,8 +290,6 @@ __global__ __launch_bounds__(kLgcnBlock) void lgcn_step_loss_kernel(const int64_
     }
 }
 
-inline unsigned lgcn_grid(int64_t n, int64_t per = kLgcnBlock) { return (unsigned)((n + per - 1) / per); }
-
 // ---- host: the graph on the device ----------------------------------------------------------------------------------------------------
 // the lane group, the vector width and the column count of a hop of width d
 struct LgcnShape {
@@ -415,8 +413,8 @@ template <int VEC, int NC, class EPI>
 void lgcn_hop_as(const LgcnGraphDev &gd, int d, int G, const float *hin, const EPI &o, hipStream_t stream) {
     const LgcnGraph g = gd.view();
     const int64_t per = kLgcnBlock / G;
-    lgcn_hop_kernel<VEC, NC, EPI><<<lgcn_grid(g.n_nodes + g.n_pieces, per), kLgcnBlock, 0, stream>>>(g, d, G, hin, gd.part.p, o);
-    if (g.n_split) lgcn_combine_kernel<VEC, NC, EPI><<<lgcn_grid(g.n_split, per), kLgcnBlock, 0, stream>>>(g, d, G, gd.part.p, o);
+    lgcn_hop_kernel<VEC, NC, EPI><<<grid(g.n_nodes + g.n_pieces, per), kLgcnBlock, 0, stream>>>(g, d, G, hin, gd.part.p, o);
+    if (g.n_split) lgcn_combine_kernel<VEC, NC, EPI><<<grid(g.n_split, per), kLgcnBlock, 0, stream>>>(g, d, G, gd.part.p, o);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -490,19 +488,19 @@ struct LgcnEpoch {
         users.upload(u, (size_t)total, stream);
         pn.upload(h_pn.data(), (size_t)(2 * total), stream);
         step_ptr.upload(sp, (size_t)steps + 1, stream);
-        lgcn_order_kernel<<<dim3((unsigned)steps, lgcn_grid(2 * max_n), 2), kLgcnBlock, 0, stream>>>(step_ptr.p, users.p, pn.p, order_u.p,
-                                                                                                   sorted_u.p, order_i.p, sorted_i.p);
+        lgcn_order_kernel<<<dim3((unsigned)steps, grid(2 * max_n), 2), kLgcnBlock, 0, stream>>>(step_ptr.p, users.p, pn.p, order_u.p,
+                                                                                                sorted_u.p, order_i.p, sorted_i.p);
         HIP_CHECK(hipGetLastError());
     }
 
     // a step's loss terms, then the gradient rows at the final embeddings E [n_nodes x d] into G
     void loss_and_gradient(const float *E, int d, int64_t n_users, int64_t n_nodes, int64_t base, int64_t n, float lambda, float *G,
                            hipStream_t stream) {
-        lgcn_loss_kernel<<<lgcn_grid(n, kLgcnBlock / 64), kLgcnBlock, 0, stream>>>(E, d, n_users, (int)n, users.p + base, pn.p + 2 * base, sig.p,
-                                                                                  bpr_t.p + base, reg_t.p + base);
-        lgcn_grad_kernel<<<lgcn_grid(n_nodes * d), kLgcnBlock, 0, stream>>>(E, d, n_users, n_nodes * d, (int)n, users.p + base, pn.p + 2 * base,
-                                                                            order_u.p + base, sorted_u.p + base, order_i.p + 2 * base,
-                                                                            sorted_i.p + 2 * base, sig.p, lambda, G);
+        lgcn_loss_kernel<<<grid(n, kLgcnBlock / 64), kLgcnBlock, 0, stream>>>(E, d, n_users, (int)n, users.p + base, pn.p + 2 * base, sig.p,
+                                                                              bpr_t.p + base, reg_t.p + base);
+        lgcn_grad_kernel<<<grid(n_nodes * d), kLgcnBlock, 0, stream>>>(E, d, n_users, n_nodes * d, (int)n, users.p + base, pn.p + 2 * base,
+                                                                       order_u.p + base, sorted_u.p + base, order_i.p + 2 * base,
+                                                                       sorted_i.p + 2 * base, sig.p, lambda, G);
         HIP_CHECK(hipGetLastError());
     }
 
@@ -520,12 +518,6 @@ struct LgcnEpoch {
         }
     }
 };
-
-// torch.optim.Adam's defaults at step t (betas 0.9 / 0.999, eps 1e-8)
-inline VaeAdam lgcn_adam_at(int64_t t, float lr) {
-    const double bc1 = 1.0 - std::pow(0.9, (double)t), bc2 = 1.0 - std::pow(0.999, (double)t);
-    return VaeAdam{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
-}
 
 }  // namespace
 }  // namespace chip

@@ -177,11 +177,11 @@ int cornac_hip_lightgcn_fit_epoch(cornac_hip_lightgcn_t h, int64_t steps, const 
         for (int64_t s = 0; s < steps; ++s) {
             const int64_t base = step_ptr[s], n = step_ptr[s + 1] - base;
             h->t += 1;
-            const VaeAdam adam = lgcn_adam_at(h->t, lr);
+            const VaeAdam adam = adam_at(h->t, lr);
             lgcn_propagate(h, h->w.p, h->E.p);
             h->ep.loss_and_gradient(h->E.p, h->d, h->n_users, h->g.n_nodes, base, n, lambda_reg, h->Gr.p, h->stream);
             lgcn_propagate(h, h->Gr.p, h->gs.p);
-            lgcn_adam_kernel<<<lgcn_grid(h->total), kLgcnBlock, 0, h->stream>>>(h->w.p, h->m.p, h->v.p, h->gs.p, h->total, adam);
+            lgcn_adam_kernel<<<grid(h->total), kLgcnBlock, 0, h->stream>>>(h->w.p, h->m.p, h->v.p, h->gs.p, h->total, adam);
             HIP_CHECK(hipGetLastError());
         }
         h->ep.losses(steps, (double)lambda_reg, loss_out, bpr_out, reg_out, h->stream);

@@ -24,9 +24,8 @@
 // positive is followed, in the reference's layout [positives | negatives, user-major], by num_neg items uniform among those
 // j for which (u, j) is not stored with a value > 0: kNcfTries Philox draws (keyed by seed, epoch, sample, try), then, if
 // all were refused, exactly the r-th admissible item, r uniform, by a walk over the row's entries.  No unbounded loop.
-#include "sparse_model.h"
 #include "rng.h"
-#include "vae_device.h"
+#include "vae_host.h"
 
 namespace chip {
 namespace {
@@ -639,8 +638,6 @@ int cornac_hip_ncf_reset_optimizer(cornac_hip_ncf_t h) {
     });
 }
 
-static unsigned ncf_grid(int64_t n, int per = kVaeBlock) { return (unsigned)((n + per - 1) / per); }
-
 static void ncf_ensure_epoch(cornac_hip_ncf_t h, int64_t samples, int64_t steps) {
     const char *nm = ncf_name(h), *what = "an epoch's samples";
     if (samples > h->cap_samples) {
@@ -678,7 +675,7 @@ static void ncf_train(cornac_hip_ncf_t h, int64_t steps, const int64_t *step_ptr
     int64_t max_n = 0;
     for (int64_t s = 0; s < steps; ++s) max_n = std::max(max_n, step_ptr[s + 1] - step_ptr[s]);
     ncf_ensure_step(h, max_n);
-    ncf_order_kernel<<<dim3((unsigned)steps, ncf_grid(max_n), 2), kVaeBlock, 0, h->stream>>>(
+    ncf_order_kernel<<<dim3((unsigned)steps, grid(max_n), 2), kVaeBlock, 0, h->stream>>>(
         h->step_ptr.p, h->users.p, h->items.p, h->order_u.p, h->sorted_u.p, h->order_i.p, h->sorted_i.p);
     HIP_CHECK(hipGetLastError());
     for (int64_t s = 0; s < steps; ++s) {
@@ -686,12 +683,11 @@ static void ncf_train(cornac_hip_ncf_t h, int64_t steps, const int64_t *step_ptr
         h->t += 1;
         NcfOpt opt{};
         opt.learner = learner; opt.lr = lr; opt.reg = reg;
-        const double bc1 = 1.0 - std::pow(0.9, (double)h->t), bc2 = 1.0 - std::pow(0.999, (double)h->t);
-        opt.adam = VaeAdam{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
-        ncf_forward_kernel<true><<<ncf_grid(n, kNcfTile), kVaeBlock, 0, h->stream>>>(
+        opt.adam = adam_at(h->t, lr);
+        ncf_forward_kernel<true><<<grid(n, kNcfTile), kVaeBlock, 0, h->stream>>>(
             h->N, h->w.p, h->users.p + base, h->items.p + base, h->n_items, n, h->labels.p + base, 1.0f / (float)n, nullptr, h->hbuf.p,
             h->dbuf.p, h->gabuf.p, h->hg.p, h->gu.p, h->gi.p, h->dl.p, h->loss.p + base);
-        ncf_sweep_kernel<<<ncf_grid(h->small_total, kNcfSlices) + ncf_grid(h->emb_total), kVaeBlock, 0, h->stream>>>(
+        ncf_sweep_kernel<<<grid(h->small_total, kNcfSlices) + grid(h->emb_total), kVaeBlock, 0, h->stream>>>(
             h->N, h->emb, h->emb_total, h->small, h->small_total, h->w.p, h->s1.p, h->s2.p, (int)n, h->order_u.p + base, h->sorted_u.p + base,
             h->order_i.p + base, h->sorted_i.p + base, h->hbuf.p, h->gabuf.p, h->hg.p, h->gu.p, h->gi.p, h->dl.p, opt);
         HIP_CHECK(hipGetLastError());
@@ -754,9 +750,9 @@ static std::vector<int64_t> ncf_draw(cornac_hip_ncf_t h, int64_t batch_size, int
     for (int64_t s = 0; s <= steps; ++s) ptr[(size_t)s] = std::min(s * batch_size, h->nnz) * per;
     ncf_ensure_epoch(h, total, steps);
     h->step_ptr.upload(ptr.data(), (size_t)steps + 1, h->stream);
-    ncf_draw_kernel<<<ncf_grid(total), kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->ent_user.p, h->n_pos.p,
-                                                                  h->nnz, h->n_items, batch_size, num_neg, seed, epoch, h->users.p,
-                                                                  h->items.p, h->labels.p);
+    ncf_draw_kernel<<<grid(total), kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->rows.val.p, h->ent_user.p, h->n_pos.p,
+                                                              h->nnz, h->n_items, batch_size, num_neg, seed, epoch, h->users.p,
+                                                              h->items.p, h->labels.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(h->stream));   // (ptr is the upload's source)
     return ptr;
@@ -799,7 +795,7 @@ static void ncf_predict(cornac_hip_ncf_t h, const int32_t *users, const int32_t 
     const int64_t width = items ? 1 : I;
     if (h->out.n < (size_t)(B * width)) alloc_named(h->out, (size_t)(B * width), nm, "the scores");
     for_each_chunk(nm, *h, users, items, n, B, [&](int64_t b0, int64_t nb) {
-        ncf_forward_kernel<false><<<ncf_grid(nb * width, kNcfTile), kVaeBlock, 0, h->stream>>>(
+        ncf_forward_kernel<false><<<grid(nb * width, kNcfTile), kVaeBlock, 0, h->stream>>>(
             h->N, h->w.p, h->user_ids.p, items ? h->item_ids.p : nullptr, I, nb * width, nullptr, 0.f, h->out.p, nullptr, nullptr, nullptr,
             nullptr, nullptr, nullptr, nullptr, nullptr);
         h->out.download(out + b0 * width, (size_t)(nb * width), h->stream);

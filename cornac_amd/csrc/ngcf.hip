@@ -342,21 +342,21 @@ static const float *ngcf_input(cornac_hip_ngcf_t h, int l) { return l == 0 ? h->
 // E from the parameters; train: with the dropout of Adam step h->t
 static void ngcf_forward(cornac_hip_ngcf_t h, bool train) {
     const int64_t N = h->N;
-    ngcf_copy0_kernel<<<lgcn_grid(N * h->d0), kLgcnBlock, 0, h->stream>>>(h->w.p, N * h->d0, h->d0, h->D, h->E.p);
+    ngcf_copy0_kernel<<<grid(N * h->d0), kLgcnBlock, 0, h->stream>>>(h->w.p, N * h->d0, h->d0, h->D, h->E.p);
     for (int l = 0; l < h->L; ++l) {
         NgcfLayer &y = h->layers[(size_t)l];
         const float *X = ngcf_input(h, l), *w = h->w.p;
         lgcn_hop(h->g, y.din, X, NgcfFwd{X, y.S.p, y.P1.p, y.P2.p}, h->stream);
         const NgcfDrop dr = ngcf_drop(h, l, train);
-        const unsigned rows = lgcn_grid(N, kBM);
+        const unsigned rows = grid(N, kBM);
         if (y.dout <= kBN) {
             ngcf_dense_kernel<true><<<dim3(rows, 1), kWb, 0, h->stream>>>(y.P1.p, y.P2.p, w + y.oW1, w + y.ob1, w + y.oW2, w + y.ob2, h->crow.p, N,
                                                                          y.din, y.dout, y.Z.p, y.Y.p, y.nrm.p, h->E.p, h->D, y.off, dr);
         } else {
-            ngcf_dense_kernel<false><<<dim3(rows, lgcn_grid(y.dout, kBN)), kWb, 0, h->stream>>>(
+            ngcf_dense_kernel<false><<<dim3(rows, grid(y.dout, kBN)), kWb, 0, h->stream>>>(
                 y.P1.p, y.P2.p, w + y.oW1, w + y.ob1, w + y.oW2, w + y.ob2, h->crow.p, N, y.din, y.dout, y.Z.p, y.Y.p, y.nrm.p, h->E.p, h->D,
                 y.off, dr);
-            ngcf_act_kernel<<<lgcn_grid(N, kLgcnBlock / 64), kLgcnBlock, 0, h->stream>>>(y.Z.p, N, y.dout, y.Y.p, y.nrm.p, h->E.p, h->D, y.off, dr);
+            ngcf_act_kernel<<<grid(N, kLgcnBlock / 64), kLgcnBlock, 0, h->stream>>>(y.Z.p, N, y.dout, y.Y.p, y.nrm.p, h->E.p, h->D, y.off, dr);
         }
         HIP_CHECK(hipGetLastError());
     }
@@ -369,16 +369,16 @@ static void ngcf_backward(cornac_hip_ngcf_t h) {
     for (int l = h->L - 1; l >= 0; --l) {
         NgcfLayer &y = h->layers[(size_t)l];
         const float *w = h->w.p;
-        ngcf_gz_kernel<<<lgcn_grid(N, kLgcnBlock / 64), kLgcnBlock, 0, h->stream>>>(y.Y.p, y.Z.p, y.nrm.p, h->GE.p, h->D, y.off, gin, N, y.dout,
-                                                                                   h->GZ.p, ngcf_drop(h, l, true));
-        const unsigned tiles = lgcn_grid(y.dout, kBM) * lgcn_grid(y.din, kBN);
+        ngcf_gz_kernel<<<grid(N, kLgcnBlock / 64), kLgcnBlock, 0, h->stream>>>(y.Y.p, y.Z.p, y.nrm.p, h->GE.p, h->D, y.off, gin, N, y.dout,
+                                                                               h->GZ.p, ngcf_drop(h, l, true));
+        const unsigned tiles = grid(y.dout, kBM) * grid(y.din, kBN);
         ngcf_wgrad_kernel<<<dim3((unsigned)h->chunks, tiles, 2), kWb, 0, h->stream>>>(h->GZ.p, y.P1.p, y.P2.p, N, y.din, y.dout, h->wpart.p, y.seg,
                                                                                      0, y.oW2 - y.oW1);
         ngcf_bgrad_kernel<<<(unsigned)h->chunks, kLgcnBlock, 0, h->stream>>>(h->GZ.p, h->crow.p, N, y.dout, h->wpart.p, y.seg, y.ob1 - y.oW1,
                                                                             y.ob2 - y.oW1);
-        ngcf_wreduce_kernel<<<lgcn_grid(y.seg), kLgcnBlock, 0, h->stream>>>(h->wpart.p, y.seg, h->chunks, h->grad.p + y.oW1);
-        ngcf_back_kernel<<<dim3(lgcn_grid(N, kBM), lgcn_grid(y.din, kBN)), kWb, 0, h->stream>>>(h->GZ.p, w + y.oW1, w + y.oW2, ngcf_input(h, l),
-                                                                                               y.S.p, N, y.din, y.dout, h->T.p, h->R.p);
+        ngcf_wreduce_kernel<<<grid(y.seg), kLgcnBlock, 0, h->stream>>>(h->wpart.p, y.seg, h->chunks, h->grad.p + y.oW1);
+        ngcf_back_kernel<<<dim3(grid(N, kBM), grid(y.din, kBN)), kWb, 0, h->stream>>>(h->GZ.p, w + y.oW1, w + y.oW2, ngcf_input(h, l),
+                                                                                      y.S.p, N, y.din, y.dout, h->T.p, h->R.p);
         HIP_CHECK(hipGetLastError());
         float *out = l == 0 ? h->grad.p : (gin == h->gya.p ? h->gyb.p : h->gya.p);
         lgcn_hop(h->g, y.din, h->T.p, NgcfBwd{h->R.p, l == 0 ? h->GE.p : nullptr, h->D, 0, out}, h->stream);
@@ -552,8 +552,8 @@ int cornac_hip_ngcf_fit_epoch(cornac_hip_ngcf_t h, int64_t steps, const int64_t 
             ngcf_forward(h, true);
             h->ep.loss_and_gradient(h->E.p, h->D, h->n_users, h->N, base, n, lambda_reg, h->GE.p, h->stream);
             ngcf_backward(h);
-            lgcn_adam_kernel<<<lgcn_grid(h->n_params), kLgcnBlock, 0, h->stream>>>(h->w.p, h->m.p, h->v.p, h->grad.p, h->n_params,
-                                                                                  lgcn_adam_at(h->t, lr));
+            lgcn_adam_kernel<<<grid(h->n_params), kLgcnBlock, 0, h->stream>>>(h->w.p, h->m.p, h->v.p, h->grad.p, h->n_params,
+                                                                              adam_at(h->t, lr));
             HIP_CHECK(hipGetLastError());
         }
         h->ep.losses(steps, (double)lambda_reg, loss_out, bpr_out, reg_out, h->stream);

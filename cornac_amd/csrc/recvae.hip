@@ -23,14 +23,15 @@
 // The old encoder's posterior is a function of the user alone between two update_prior calls: it is computed for every
 // user once per update_prior with the forward kernels above and read per step.  Batches are arbitrary user ids, so each
 // pass lists every item's entries in the pass's order (a counting sort on the host, one upload); a step's users are then a
-// range of that list found by bisection, as in vaecf.hip.  No float atomics; every sum has one fixed order (thread-owned
-// chains in ascending index, fixed trees in a workgroup): the same inputs give the same bits.  Offsets are 64-bit.
+// range of that list found by bisection, as in vae_device.h's vae_w1_adam_kernel.  No float atomics; every sum has one fixed
+// order (thread-owned chains in ascending index, fixed trees in a workgroup): the same inputs give the same bits.  Offsets
+// are 64-bit.
 //
-// The dense products are register-tiled vector FMA (64 x 64 tiles, 4 x 4 per thread, operands staged through LDS) as in
-// vaecf.hip: f32-input MFMA has vector FMA's peak on this part, and the chains keep a fixed ascending order this way.
-#include "sparse_model.h"
+// The dense products are vae_device.h's register-tiled vector FMA (64 x 64 tiles, 4 x 4 per thread, operands staged through
+// LDS), launched by vae_host.h's linear, linear_back, linear_back_split and weight_adam: f32-input MFMA has vector FMA's peak
+// on this part, and the chains keep a fixed ascending order this way.
 #include "rng.h"
-#include "vae_device.h"
+#include "vae_host.h"
 
 #include <memory>
 
@@ -38,7 +39,7 @@ namespace chip {
 namespace {
 
 constexpr int kRvMaxK = 256, kRvMaxH = 1024, kRvMaxBatch = 1024;
-constexpr int kRvTile = 64, kRvTk = 16, kRvLayers = 5, kRvEncTables = 24, kRvTrainTables = 26, kRvTables = 53;
+constexpr int kRvLayers = 5, kRvEncTables = 24, kRvTrainTables = 26, kRvTables = 53;
 constexpr int kRvPerThread = kRvMaxH / kVaeBlock;
 constexpr int kRvChunk = 512;   // entries of a row per workgroup of the input layer
 constexpr float kRvLnEps = 0.1f, kRvLog2Pi = 1.8378770664093453f;
@@ -49,42 +50,14 @@ struct RvLayout {
     int64_t W[kRvLayers], b[kRvLayers], g[kRvLayers], c[kRvLayers], Wm, bm, Wv, bv, enc_total, Wd, bd, total;
 };
 
-__device__ inline float rv_block_sum(float v, float *sh) {   // fixed tree over the workgroup's 256 values
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = kVaeBlock / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ inline float rv_block_max(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = kVaeBlock / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] = fmaxf(sh[t], sh[t + s]);
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 // ---- draws on the device: pure functions of (seed, pass key, entry) and (seed, pass key, user, column) ---------------------
-__device__ inline float rv_unit(uint32_t r) { return ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
 __global__ void rv_keep_kernel(uint8_t *keep, int64_t nnz, float keep_share, uint64_t key, uint64_t seed) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nnz) return;
     uint32_t r[4];
     philox4x32_10((uint32_t)e, (uint32_t)((uint64_t)e >> 32), (uint32_t)key, (uint32_t)(key >> 32) ^ 0x6b656570u, (uint32_t)seed,
                   (uint32_t)(seed >> 32), r);
-    keep[e] = rv_unit(r[0]) < keep_share ? 1 : 0;
+    keep[e] = unit(r[0]) < keep_share ? 1 : 0;
 }
 
 __global__ void rv_noise_kernel(float *eps, int64_t n_users, int k, uint64_t key, uint64_t seed) {
@@ -92,7 +65,7 @@ __global__ void rv_noise_kernel(float *eps, int64_t n_users, int k, uint64_t key
     if (e >= n_users * k) return;
     uint32_t r[4];
     philox4x32_10((uint32_t)(e / k), (uint32_t)(e % k), (uint32_t)key, (uint32_t)(key >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    eps[e] = 0.01f * (sqrtf(-2.f * logf(rv_unit(r[0]))) * cosf(6.283185307179586f * rv_unit(r[1])));
+    eps[e] = 0.01f * normal(r[0], r[1]);
 }
 
 // ---- input: one workgroup per user and chunk of kRvChunk of its entries ------------------------------------------------------
@@ -156,7 +129,7 @@ __global__ __launch_bounds__(kVaeBlock) void rv_layer_kernel(const float *__rest
             acc += s[q];
         }
     }
-    const float mean = rv_block_sum(acc, sh) / (float)h;
+    const float mean = block_sum(acc, sh) / (float)h;
     acc = 0.f;
 #pragma unroll
     for (int q = 0; q < kRvPerThread; ++q) {
@@ -166,7 +139,7 @@ __global__ __launch_bounds__(kVaeBlock) void rv_layer_kernel(const float *__rest
             acc += s[q] * s[q];
         }
     }
-    const float r = 1.f / sqrtf(rv_block_sum(acc, sh) / (float)h + kRvLnEps);
+    const float r = 1.f / sqrtf(block_sum(acc, sh) / (float)h + kRvLnEps);
     if (threadIdx.x == 0) rstd[b] = r;
 #pragma unroll
     for (int q = 0; q < kRvPerThread; ++q) {
@@ -199,7 +172,7 @@ __global__ __launch_bounds__(kVaeBlock) void rv_layer_back_kernel(const float *_
             a2 += gx[q] * xh[q];
         }
     }
-    const float m1 = rv_block_sum(a1, sh) / (float)h, m2 = rv_block_sum(a2, sh) / (float)h, r = rstd[b];
+    const float m1 = block_sum(a1, sh) / (float)h, m2 = block_sum(a2, sh) / (float)h, r = rstd[b];
 #pragma unroll
     for (int q = 0; q < kRvPerThread; ++q) {
         const int j = threadIdx.x + q * kVaeBlock;
@@ -209,78 +182,6 @@ __global__ __launch_bounds__(kVaeBlock) void rv_layer_back_kernel(const float *_
             const float v = gs * (sg * (1.f + x * (1.f - sg)));
             gp[b * h + j] = v;
             S[b * h + j] = last ? v : S[b * h + j] + v;
-        }
-    }
-}
-
-// ---- the products -----------------------------------------------------------------------------------------------------------
-// C[M x N] = sum_k A(m, k) B(k, n) over k in [z kchunk, (z + 1) kchunk), ascending; A(m, k) = A[m a_sm + k a_sk] and
-// B(k, n) = B[k b_sk + n b_sn]; AK / BK say that the operand is contiguous along k (the staging loads follow it).
-// EPI 0: C[m N + n] = acc (+ bias[n]) (+ add[m N + n]);  1: C[(z M + m) N + n] = acc;  2: Adam on w / m / v [m N + n], g = acc.
-template <bool AK, bool BK, int EPI>
-__global__ __launch_bounds__(kVaeBlock) void rv_gemm_kernel(const float *__restrict__ A, int64_t a_sm, int64_t a_sk,
-                                                            const float *__restrict__ B, int64_t b_sk, int64_t b_sn, int64_t M, int64_t N,
-                                                            int64_t K, int64_t kchunk, float *C, const float *bias, const float *add,
-                                                            float *am, float *av, VaeAdam ad) {
-    __shared__ float sA[kRvTk][kRvTile + 4];
-    __shared__ float sB[kRvTk][kRvTile + 4];
-    const int64_t tiles_n = (N + kRvTile - 1) / kRvTile;
-    const int64_t n0 = ((int64_t)blockIdx.x % tiles_n) * kRvTile, m0 = ((int64_t)blockIdx.x / tiles_n) * kRvTile;
-    const int64_t k_begin = (int64_t)blockIdx.z * kchunk, k_end = K < k_begin + kchunk ? K : k_begin + kchunk;
-    const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
-    float acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += kRvTk) {
-#pragma unroll
-        for (int q = 0; q < kRvTile * kRvTk / kVaeBlock; ++q) {
-            const int idx = threadIdx.x + kVaeBlock * q;
-            const int kk = AK ? idx % kRvTk : idx / kRvTile, mm = AK ? idx / kRvTk : idx % kRvTile;
-            const int64_t gm = m0 + mm, gk = k0 + kk;
-            sA[kk][mm] = (gm < M && gk < k_end) ? A[gm * a_sm + gk * a_sk] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < kRvTile * kRvTk / kVaeBlock; ++q) {
-            const int idx = threadIdx.x + kVaeBlock * q;
-            const int kk = BK ? idx % kRvTk : idx / kRvTile, nn = BK ? idx / kRvTk : idx % kRvTile;
-            const int64_t gn = n0 + nn, gk = k0 + kk;
-            sB[kk][nn] = (gn < N && gk < k_end) ? B[gk * b_sk + gn * b_sn] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kRvTk; ++kk) {
-            float a[4], b[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a[q] = sA[kk][ty * 4 + q];
-                b[q] = sB[kk][tx * 4 + q];
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fmaf(a[p], b[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int64_t gm = m0 + ty * 4 + p;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t gn = n0 + tx * 4 + q;
-            if (gm >= M || gn >= N) continue;
-            if (EPI == 0) {
-                float v = acc[p][q];
-                if (bias) v += bias[gn];
-                if (add) v += add[gm * N + gn];
-                C[gm * N + gn] = v;
-            } else if (EPI == 1) {
-                C[((int64_t)blockIdx.z * M + gm) * N + gn] = acc[p][q];
-            } else {
-                vae_adam(C, am, av, gm * N + gn, acc[p][q], ad);
-            }
         }
     }
 }
@@ -328,7 +229,7 @@ __global__ __launch_bounds__(kVaeBlock) void rv_latent_kernel(const int32_t *__r
         z[b * k + c] = zz;
         t = rv_kl(zz, m, l, pri[c], pri[k + c], post_mu[u * k + c], post_lv[u * k + c], pri[2 * k + c]).term;
     }
-    t = rv_block_sum(t, sh);
+    t = block_sum(t, sh);
     if (threadIdx.x == 0) kld[b] = (gamma != 0.f ? gamma * sumx[u] : beta) * t;
 }
 
@@ -365,14 +266,14 @@ __global__ __launch_bounds__(kVaeBlock) void rv_likelihood_kernel(const int64_t 
     float *row = o + b * I;
     float mx = -INFINITY;
     for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) mx = fmaxf(mx, row[i]);
-    mx = rv_block_max(mx, sh);
+    mx = block_max(mx, sh);
     float se = 0.f;
     for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) se += expf(row[i] - mx);
-    se = rv_block_sum(se, sh);
+    se = block_sum(se, sh);
     const float lse = mx + logf(se);
     float ll = 0.f;
     for (int64_t e = lo + threadIdx.x; e < hi; e += kVaeBlock) ll += x[e] * (row[row_idx[e]] - lse);
-    ll = rv_block_sum(ll, sh);   // (its barriers also order the reads above before the stores below)
+    ll = block_sum(ll, sh);   // (its barriers also order the reads above before the stores below)
     if (threadIdx.x == 0) mll[b] = ll;
     const float sx = sumx[u] * inv_b;
     for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) row[i] = expf(row[i] - mx) / se * sx;
@@ -423,11 +324,6 @@ __global__ void rv_w1_adam_kernel(float *w, float *am, float *av, int64_t I, int
         g = fmaf(x, gp[((int64_t)col_pos[lo] - p0) * h + j], g);
     }
     vae_adam(w, am, av, e, g, ad);
-}
-
-__global__ void rv_gather_pairs_kernel(const float *__restrict__ p, int64_t I, const int32_t *__restrict__ items, int64_t n, float *out) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) out[q] = p[q * I + items[q]];
 }
 
 __global__ void rv_iota_kernel(int32_t *out, int64_t n) {
@@ -487,30 +383,6 @@ static void rv_enc_table(cornac_hip_recvae_t h, int q, int64_t *off, int64_t *ro
     }
 }
 
-// host <-> device copy of one table in the reference's shape; fc1.weight is [h x I] there, [I x h] here
-static void rv_put(cornac_hip_recvae_t h, float *dst, const float *src, int64_t rows, int64_t cols, bool transposed) {
-    std::vector<float> t;
-    if (transposed) {
-        t.resize((size_t)(rows * cols));
-        for (int64_t j = 0; j < rows; ++j)
-            for (int64_t i = 0; i < cols; ++i) t[(size_t)(i * rows + j)] = src[j * cols + i];
-        src = t.data();
-    }
-    HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)(rows * cols) * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
-static void rv_get(cornac_hip_recvae_t h, const float *src, float *dst, int64_t rows, int64_t cols, bool transposed) {
-    const size_t n = (size_t)(rows * cols);
-    std::vector<float> t;
-    if (transposed) t.resize(n);
-    HIP_CHECK(hipMemcpyAsync(transposed ? t.data() : dst, src, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    if (transposed)
-        for (int64_t j = 0; j < rows; ++j)
-            for (int64_t i = 0; i < cols; ++i) dst[j * cols + i] = t[(size_t)(i * rows + j)];
-}
-
 // the 26 trainable tables (encoder's 24, decoder.weight, decoder.bias) of `buf` (w, m or v) to the host
 static void rv_get_trainable(cornac_hip_recvae_t h, const DevBuf<float> &buf, float *const *tables) {
     for (int q = 0; q < kRvTrainTables; ++q) {
@@ -518,7 +390,7 @@ static void rv_get_trainable(cornac_hip_recvae_t h, const DevBuf<float> &buf, fl
         int64_t off, rows, cols;
         if (q < kRvEncTables) rv_enc_table(h, q, &off, &rows, &cols);
         else { off = q == kRvEncTables ? h->L.Wd : h->L.bd; rows = q == kRvEncTables ? h->n_items : 1; cols = q == kRvEncTables ? h->k : h->n_items; }
-        rv_get(h, buf.p + off, tables[q], rows, cols, q == 0);
+        get_table(h->stream, buf.p + off, tables[q], rows, cols, q == 0);
     }
 }
 
@@ -526,7 +398,7 @@ static void rv_ensure(cornac_hip_recvae_t h, int64_t cap) {
     if (cap <= h->cap) return;
     const size_t I = (size_t)h->n_items, hh = (size_t)h->h, k = (size_t)h->k, c = (size_t)cap;
     h->n_split = (int)std::min<int64_t>(32, std::max<int64_t>(1, (h->n_items + 1023) / 1024));
-    h->kchunk = ((h->n_items + h->n_split - 1) / h->n_split + kRvTk - 1) / kRvTk * kRvTk;
+    h->kchunk = ((h->n_items + h->n_split - 1) / h->n_split + kVaeTk - 1) / kVaeTk * kVaeTk;
     const char *what = "a batch's activations and logits";
     h->cap = 0;
     alloc_named(h->act, (size_t)(5 * kRvLayers + 2) * c * hh, "RecVAE", what);
@@ -538,50 +410,21 @@ static void rv_ensure(cornac_hip_recvae_t h, int64_t cap) {
     h->cap = cap;
 }
 
-static unsigned rv_grid(int64_t n) { return (unsigned)((n + kVaeBlock - 1) / kVaeBlock); }
-
-static unsigned rv_tiles(int64_t M, int64_t N) {
-    const int64_t t = ((M + kRvTile - 1) / kRvTile) * ((N + kRvTile - 1) / kRvTile);
-    REQUIRE(t < (1ll << 31), "RecVAE: %lld x %lld is more than a product's grid holds", (long long)M, (long long)N);
-    return (unsigned)t;
-}
-
-// C[M x N] = A[M x K] W[N x K]^T (+ bias) (+ add): a Linear layer's forward
-static void rv_linear(cornac_hip_recvae_t h, const float *A, const float *W, const float *bias, const float *add, int64_t M, int64_t N,
-                      int64_t K, float *C) {
-    rv_gemm_kernel<true, true, 0><<<dim3(rv_tiles(M, N)), kVaeBlock, 0, h->stream>>>(A, K, 1, W, 1, K, M, N, K, K + kRvTk, C, bias, add, nullptr,
-                                                                                    nullptr, VaeAdam{});
-}
-
-// C[M x N] = A[M x K] W[K x N] (+ add): a Linear layer's backward in its input
-static void rv_linear_back(cornac_hip_recvae_t h, const float *A, const float *W, const float *add, int64_t M, int64_t N, int64_t K,
-                           float *C) {
-    rv_gemm_kernel<true, false, 0><<<dim3(rv_tiles(M, N)), kVaeBlock, 0, h->stream>>>(A, K, 1, W, N, 1, M, N, K, K + kRvTk, C, nullptr, add,
-                                                                                     nullptr, nullptr, VaeAdam{});
-}
-
-// Adam on W[N x K] with g = Gy[nb x N]^T X[nb x K], each tile applied at once
-static void rv_weight_adam(cornac_hip_recvae_t h, const float *Gy, const float *X, int64_t nb, int64_t N, int64_t K, int64_t at,
-                           const VaeAdam &ad) {
-    rv_gemm_kernel<false, false, 2><<<dim3(rv_tiles(N, K)), kVaeBlock, 0, h->stream>>>(Gy, 1, N, X, K, 1, N, K, nb, nb + kRvTk, h->w.p + at, nullptr,
-                                                                                      nullptr, h->m.p + at, h->v.p + at, ad);
-}
-
 // the encoder `enc` (the trained one or the old one) over the rows users[0 .. nb): pre / xhat / hid / rstd of every layer, mu, lv
 static void rv_forward(cornac_hip_recvae_t h, const float *enc, const int32_t *users, int64_t nb, const uint8_t *keep, float scale) {
     const RvLayout &L = h->L;
     const int64_t hh = h->h, k = h->k;
     rv_input_kernel<<<dim3((unsigned)nb, (unsigned)h->n_chunks), kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->xn.p, keep, scale,
                                                                                            users, enc + L.W[0], (int)hh, h->part_in.p);
-    rv_input_sum_kernel<<<rv_grid(nb * hh), kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, users, h->part_in.p, h->n_chunks, enc + L.b[0], (int)hh, nb,
-                                                                      h->pre(0));
+    rv_input_sum_kernel<<<grid(nb * hh), kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, users, h->part_in.p, h->n_chunks, enc + L.b[0], (int)hh, nb,
+                                                                    h->pre(0));
     for (int l = 0; l < kRvLayers; ++l) {
-        if (l > 0) rv_linear(h, h->hid(l - 1), enc + L.W[l], enc + L.b[l], h->R(), nb, hh, hh, h->pre(l));
+        if (l > 0) linear(h->stream, "RecVAE", h->hid(l - 1), enc + L.W[l], enc + L.b[l], h->R(), nb, hh, hh, h->pre(l));
         rv_layer_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->pre(l), (int)hh, enc + L.g[l], enc + L.c[l], h->xhat(l),
                                                                   h->rstd.p + (size_t)l * (size_t)h->cap, h->hid(l), h->R(), l == 0);
     }
-    rv_linear(h, h->hid(kRvLayers - 1), enc + L.Wm, enc + L.bm, nullptr, nb, k, hh, h->mu.p);
-    rv_linear(h, h->hid(kRvLayers - 1), enc + L.Wv, enc + L.bv, nullptr, nb, k, hh, h->lv.p);
+    linear(h->stream, "RecVAE", h->hid(kRvLayers - 1), enc + L.Wm, enc + L.bm, nullptr, nb, k, hh, h->mu.p);
+    linear(h->stream, "RecVAE", h->hid(kRvLayers - 1), enc + L.Wv, enc + L.bv, nullptr, nb, k, hh, h->lv.p);
 }
 
 // the old encoder's posterior of every user (recvae.py:35), with the kernels of the training forward
@@ -649,7 +492,7 @@ int cornac_hip_recvae_create(cornac_hip_recvae_t *out, int device, int64_t n_use
         alloc_named(h->kld, (size_t)n_users, "RecVAE", "the users' losses");
         alloc_named(h->order, (size_t)n_users, "RecVAE", "the pass's order");
         alloc_named(h->iota, (size_t)n_users, "RecVAE", "the users' ids");
-        rv_iota_kernel<<<rv_grid(n_users), kVaeBlock, 0, h->stream>>>(h->iota.p, n_users);
+        rv_iota_kernel<<<grid(n_users), kVaeBlock, 0, h->stream>>>(h->iota.p, n_users);
         // the constants of the data set (recvae.py:67, 100): x, x / max(||x||, 1e-12) and the rows' sums, in float32
         std::vector<float> x((size_t)nnz), xn((size_t)nnz), sumx((size_t)n_users);
         int64_t longest = 0;
@@ -703,17 +546,17 @@ int cornac_hip_recvae_set_params(cornac_hip_recvae_t h, const float *const *tabl
             int64_t off, rows, cols;
             if (q < kRvEncTables) {
                 rv_enc_table(h, q, &off, &rows, &cols);
-                rv_put(h, h->w.p + off, tables[q], rows, cols, q == 0);
+                put_table(h->stream, h->w.p + off, tables[q], rows, cols, q == 0);
             } else if (q < kRvEncTables + 3) {
-                rv_put(h, h->pri.p + (int64_t)(q - kRvEncTables) * h->k, tables[q], 1, h->k, false);   // (read per step)
+                put_table(h->stream, h->pri.p + (int64_t)(q - kRvEncTables) * h->k, tables[q], 1, h->k, false);   // (read per step)
             } else if (q < 2 * kRvEncTables + 3) {
                 rv_enc_table(h, q - kRvEncTables - 3, &off, &rows, &cols);
-                rv_put(h, h->old.p + off, tables[q], rows, cols, q == kRvEncTables + 3);
+                put_table(h->stream, h->old.p + off, tables[q], rows, cols, q == kRvEncTables + 3);
                 h->post_stale = true;
             } else if (q == kRvTables - 2) {
-                rv_put(h, h->w.p + h->L.Wd, tables[q], h->n_items, h->k, false);
+                put_table(h->stream, h->w.p + h->L.Wd, tables[q], h->n_items, h->k, false);
             } else {
-                rv_put(h, h->w.p + h->L.bd, tables[q], 1, h->n_items, false);
+                put_table(h->stream, h->w.p + h->L.bd, tables[q], 1, h->n_items, false);
             }
         }
     });
@@ -729,13 +572,13 @@ int cornac_hip_recvae_get_params(cornac_hip_recvae_t h, float *const *tables) {
         train[kRvEncTables + 1] = tables[kRvTables - 1];
         rv_get_trainable(h, h->w, train);
         for (int q = 0; q < 3; ++q)
-            if (tables[kRvEncTables + q]) rv_get(h, h->pri.p + (int64_t)q * h->k, tables[kRvEncTables + q], 1, h->k, false);
+            if (tables[kRvEncTables + q]) get_table(h->stream, h->pri.p + (int64_t)q * h->k, tables[kRvEncTables + q], 1, h->k, false);
         for (int q = 0; q < kRvEncTables; ++q) {
             float *dst = tables[kRvEncTables + 3 + q];
             if (!dst) continue;
             int64_t off, rows, cols;
             rv_enc_table(h, q, &off, &rows, &cols);
-            rv_get(h, h->old.p + off, dst, rows, cols, q == 0);
+            get_table(h->stream, h->old.p + off, dst, rows, cols, q == 0);
         }
     });
 }
@@ -780,11 +623,6 @@ int cornac_hip_recvae_get_prior_posterior(cornac_hip_recvae_t h, float *mu_out, 
     });
 }
 
-static VaeAdam rv_adam(float lr, int64_t t) {
-    const double bc1 = 1.0 - std::pow(0.9, (double)t), bc2 = 1.0 - std::pow(0.999, (double)t);
-    return VaeAdam{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
-}
-
 int cornac_hip_recvae_fit_epoch(cornac_hip_recvae_t h, const int32_t *order, int64_t batch_size, float lr, float gamma, float beta,
                                 float dropout_rate, int step_encoder, int step_decoder, const uint8_t *keep, const float *eps,
                                 uint64_t seed, double *step_loss) {
@@ -812,11 +650,11 @@ int cornac_hip_recvae_fit_epoch(cornac_hip_recvae_t h, const int32_t *order, int
         h->order.upload(order, (size_t)nu, h->stream);
         if (drop && nnz) {
             if (keep) h->keep.upload(keep, (size_t)nnz, h->stream);
-            else rv_keep_kernel<<<rv_grid(nnz), kVaeBlock, 0, h->stream>>>(h->keep.p, nnz, 1.f - dropout_rate, key, seed);
+            else rv_keep_kernel<<<grid(nnz), kVaeBlock, 0, h->stream>>>(h->keep.p, nnz, 1.f - dropout_rate, key, seed);
         }
         const uint8_t *kp = drop && nnz ? h->keep.p : nullptr;
         if (eps) h->eps.upload(eps, (size_t)(nu * k), h->stream);
-        else rv_noise_kernel<<<rv_grid(nu * k), kVaeBlock, 0, h->stream>>>(h->eps.p, nu, (int)k, key, seed);
+        else rv_noise_kernel<<<grid(nu * k), kVaeBlock, 0, h->stream>>>(h->eps.p, nu, (int)k, key, seed);
         std::vector<int32_t> col_pos;
         std::vector<int64_t> col_ent;
         if (step_encoder && nnz) {   // every item's entries by ascending position in this pass: a counting sort
@@ -842,26 +680,25 @@ int cornac_hip_recvae_fit_epoch(cornac_hip_recvae_t h, const int32_t *order, int
             rv_forward(h, w, users, nb, kp, scale);
             rv_latent_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(users, (int)k, h->mu.p, h->lv.p, h->eps.p, h->pri.p, h->post_mu.p,
                                                                        h->post_lv.p, h->sumx.p, gamma, beta, h->z.p, h->kld.p + p0);
-            rv_linear(h, h->z.p, w + L.Wd, w + L.bd, nullptr, nb, I, k, h->logits.p);
+            linear(h->stream, "RecVAE", h->z.p, w + L.Wd, w + L.bd, nullptr, nb, I, k, h->logits.p);
             rv_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, h->x.p, h->sumx.p, users, h->logits.p, I,
                                                                            inv_b, h->mll.p + p0);
             if (step_encoder) {
                 h->t_enc += 1;
-                const VaeAdam ad = rv_adam(lr, h->t_enc);
+                const VaeAdam ad = adam_at(h->t_enc, lr);
                 // gz partials: go[nb x I] D[I x k] over n_split item ranges
-                rv_gemm_kernel<true, false, 1><<<dim3(rv_tiles(nb, k), 1, (unsigned)h->n_split), kVaeBlock, 0, h->stream>>>(
-                    h->logits.p, I, 1, w + L.Wd, k, 1, nb, k, I, h->kchunk, h->part.p, nullptr, nullptr, nullptr, nullptr, VaeAdam{});
+                linear_back_split(h->stream, "RecVAE", h->logits.p, w + L.Wd, nb, k, I, h->kchunk, h->n_split, h->part.p);
                 rv_latent_back_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(users, (int)k, nb, h->part.p, h->n_split, h->mu.p, h->lv.p,
                                                                                 h->z.p, h->eps.p, h->pri.p, h->post_mu.p, h->post_lv.p,
                                                                                 h->sumx.p, gamma, beta, inv_b, h->gmu.p, h->glv.p);
                 const int top = kRvLayers - 1;
-                rv_linear_back(h, h->gmu.p, w + L.Wm, nullptr, nb, hh, k, h->G(top));
-                rv_linear_back(h, h->glv.p, w + L.Wv, h->G(top), nb, hh, k, h->G(top));
+                linear_back(h->stream, "RecVAE", h->gmu.p, w + L.Wm, nullptr, nb, hh, k, h->G(top));
+                linear_back(h->stream, "RecVAE", h->glv.p, w + L.Wv, h->G(top), nb, hh, k, h->G(top));
                 for (int l = top; l >= 0; --l) {
                     rv_layer_back_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->G(l), h->pre(l), h->xhat(l),
                                                                                    h->rstd.p + (size_t)l * (size_t)h->cap, (int)hh, w + L.g[l],
                                                                                    h->gp(l), h->S(), l == top);
-                    if (l > 0) rv_linear_back(h, h->gp(l), w + L.W[l], h->S(), nb, hh, hh, h->G(l - 1));
+                    if (l > 0) linear_back(h->stream, "RecVAE", h->gp(l), w + L.W[l], h->S(), nb, hh, hh, h->G(l - 1));
                 }
                 // every gradient is taken: now the encoder's Adam
                 RvVecs vs{};
@@ -873,21 +710,22 @@ int cornac_hip_recvae_fit_epoch(cornac_hip_recvae_t h, const int32_t *order, int
                 }
                 vs.v[nv++] = RvVec{h->gmu.p, nullptr, k, L.bm};
                 vs.v[nv++] = RvVec{h->glv.p, nullptr, k, L.bv};
-                rv_vec_adam_kernel<<<dim3(rv_grid(std::max(hh, k)), (unsigned)nv), kVaeBlock, 0, h->stream>>>(w, am, av, vs, nb, ad);
-                for (int l = 1; l < kRvLayers; ++l) rv_weight_adam(h, h->gp(l), h->hid(l - 1), nb, hh, hh, L.W[l], ad);
-                rv_weight_adam(h, h->gmu.p, h->hid(top), nb, k, hh, L.Wm, ad);
-                rv_weight_adam(h, h->glv.p, h->hid(top), nb, k, hh, L.Wv, ad);
-                rv_w1_adam_kernel<<<rv_grid(I * hh), kVaeBlock, 0, h->stream>>>(w + L.W[0], am + L.W[0], av + L.W[0], I, (int)hh, p0, nb,
-                                                                               h->col_ptr.p, h->col_pos.p, h->col_ent.p, h->xn.p, kp, scale,
-                                                                               h->gp(0), ad);
+                rv_vec_adam_kernel<<<dim3(grid(std::max(hh, k)), (unsigned)nv), kVaeBlock, 0, h->stream>>>(w, am, av, vs, nb, ad);
+                for (int l = 1; l < kRvLayers; ++l)
+                    weight_adam(h->stream, "RecVAE", h->gp(l), h->hid(l - 1), nb, hh, hh, w + L.W[l], am + L.W[l], av + L.W[l], ad);
+                weight_adam(h->stream, "RecVAE", h->gmu.p, h->hid(top), nb, k, hh, w + L.Wm, am + L.Wm, av + L.Wm, ad);
+                weight_adam(h->stream, "RecVAE", h->glv.p, h->hid(top), nb, k, hh, w + L.Wv, am + L.Wv, av + L.Wv, ad);
+                rv_w1_adam_kernel<<<grid(I * hh), kVaeBlock, 0, h->stream>>>(w + L.W[0], am + L.W[0], av + L.W[0], I, (int)hh, p0, nb,
+                                                                             h->col_ptr.p, h->col_pos.p, h->col_ent.p, h->xn.p, kp, scale,
+                                                                             h->gp(0), ad);
             }
             if (step_decoder) {
                 h->t_dec += 1;
-                const VaeAdam ad = rv_adam(lr, h->t_dec);
+                const VaeAdam ad = adam_at(h->t_dec, lr);
                 RvVecs vs{};
                 vs.v[0] = RvVec{h->logits.p, nullptr, I, L.bd};
-                rv_vec_adam_kernel<<<dim3(rv_grid(I), 1), kVaeBlock, 0, h->stream>>>(w, am, av, vs, nb, ad);
-                rv_weight_adam(h, h->logits.p, h->z.p, nb, I, k, L.Wd, ad);
+                rv_vec_adam_kernel<<<dim3(grid(I), 1), kVaeBlock, 0, h->stream>>>(w, am, av, vs, nb, ad);
+                weight_adam(h->stream, "RecVAE", h->logits.p, h->z.p, nb, I, k, w + L.Wd, am + L.Wd, av + L.Wd, ad);
             }
             HIP_CHECK(hipGetLastError());
         }
@@ -928,11 +766,11 @@ static void rv_predict(cornac_hip_recvae_t h, const int32_t *users, const int32_
             if (out2) h->lv.download(out2 + b0 * k, (size_t)(nb * k), h->stream);
             return;
         }
-        rv_linear(h, h->mu.p, h->w.p + h->L.Wd, h->w.p + h->L.bd, nullptr, nb, I, k, h->logits.p);
+        linear(h->stream, "RecVAE", h->mu.p, h->w.p + h->L.Wd, h->w.p + h->L.bd, nullptr, nb, I, k, h->logits.p);
         if (what == 1) {
             h->logits.download(out + b0 * I, (size_t)(nb * I), h->stream);
         } else {
-            rv_gather_pairs_kernel<<<rv_grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->item_ids.p, nb, h->out.p);
+            gather_pairs_kernel<<<grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->item_ids.p, nb, h->out.p);
             h->out.download(out + b0, (size_t)nb, h->stream);
         }
     });

@@ -1,6 +1,7 @@
-// Host scaffold of the models that score from a device handle of their own (knn.hip, ease.hip, vaecf.hip): named device
-// allocation, CSR validation / transpose / upload, the handle's device and stream, and the id-checked chunk loop of their
-// score_users / score_pairs entry points.  Host code only; every message carries the model's prefix.
+// Host scaffold of the models that score from a device handle of their own: named device allocation, CSR validation /
+// transpose / upload, the handle's device and stream, and the id-checked chunk loop of their score_users / score_pairs
+// entry points.  Included by knn.hip and ease.hip, and through vae_host.h by vaecf.hip, bivae.hip,
+// recvae.hip, ncf.hip and graph.h (lightgcn.hip, ngcf.hip).  Host code only; every message carries the model's prefix.
 #pragma once
 #include "common.h"
 

@@ -19,17 +19,16 @@
 // No float atomics; every sum has one fixed order (thread-owned chains in ascending index, fixed trees in a workgroup),
 // so the same inputs give the same bits.  Offsets into the I x h tables are 64-bit.
 //
-// The three B x h x I products are register-tiled vector FMA (64 x 64 tiles, 4 x 4 per thread, operands staged through
-// LDS): f32-input MFMA has vector FMA's peak on this part, and the chains keep a fixed ascending order this way.
-#include "sparse_model.h"
+// The three B x h x I products are vae_device.h's register-tiled vector FMA (64 x 64 tiles, 4 x 4 per thread, operands staged
+// through LDS), launched by vae_host.h's linear, linear_back_split and weight_adam: f32-input MFMA has vector FMA's peak on
+// this part, and the chains keep a fixed ascending order this way.
 #include "rng.h"
-#include "vae_device.h"
+#include "vae_host.h"
 
 namespace chip {
 namespace {
 
 constexpr int kVaeMaxK = 256, kVaeMaxH = 1024, kVaeMaxBatch = 1024;
-constexpr int kVaeTile = 64, kVaeTk = 16;
 constexpr float kVaeEps = 1e-10f;
 constexpr int64_t kVaeScoreBytes = 256ll << 20;   // a scoring chunk's logits (at most kVaeMaxBatch users)
 enum { LIK_MULT = 0, LIK_BERN, LIK_GAUS, LIK_POIS, LIK_COUNT };
@@ -38,33 +37,6 @@ enum { LIK_MULT = 0, LIK_BERN, LIK_GAUS, LIK_POIS, LIK_COUNT };
 struct VaeLayout {
     int64_t W1, b1, Wm, bm, Wv, bv, D0, c0, D1, c1, total;
 };
-
-// fixed tree over the workgroup's 256 values
-__device__ inline float vae_block_sum(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = kVaeBlock / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] += sh[t + s];
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ inline float vae_block_max(float v, float *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = kVaeBlock / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] = fmaxf(sh[t], sh[t + s]);
-        __syncthreads();
-    }
-    const float r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 __device__ inline bool vae_holds(const int32_t *__restrict__ idx, int64_t lo, int64_t hi, int32_t i) {
     const int64_t end = hi;
@@ -82,8 +54,7 @@ __global__ void vae_noise_kernel(float *eps, int64_t n_users, int k, int64_t bat
     const int64_t u = e / k, c = e % k, t = t0 + u / batch_size + 1;
     uint32_t r[4];
     philox4x32_10((uint32_t)u, (uint32_t)c, (uint32_t)t, (uint32_t)((uint64_t)t >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    eps[e] = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+    eps[e] = normal(r[0], r[1]);
 }
 
 // ---- encode: one workgroup per user ------------------------------------------------------------------------------------------
@@ -142,71 +113,6 @@ __global__ __launch_bounds__(kVaeBlock) void vae_encode_kernel(
     }
 }
 
-// ---- the three products -------------------------------------------------------------------------------------------------------
-// C[M x N] = sum_k A(m, k) B(k, n) over k in [z kchunk, (z + 1) kchunk), ascending; A(m, k) = A[m a_sm + k a_sk] and
-// B(k, n) = B[k b_sk + n b_sn]; AK / BK say that the operand is contiguous along k (the staging loads follow it).
-// EPI 0: C[m ldc + n] = acc + bias[n];  1: C[(z M + m) N + n] = acc;  2: Adam on w / m / v [m N + n] with g = acc.
-template <bool AK, bool BK, int EPI>
-__global__ __launch_bounds__(kVaeBlock) void vae_gemm_kernel(const float *__restrict__ A, int64_t a_sm, int64_t a_sk,
-                                                             const float *__restrict__ B, int64_t b_sk, int64_t b_sn, int64_t M,
-                                                             int64_t N, int64_t K, int64_t kchunk, float *C, const float *bias,
-                                                             float *am, float *av, VaeAdam ad) {
-    __shared__ float sA[kVaeTk][kVaeTile + 4];
-    __shared__ float sB[kVaeTk][kVaeTile + 4];
-    const int64_t tiles_n = (N + kVaeTile - 1) / kVaeTile;
-    const int64_t n0 = ((int64_t)blockIdx.x % tiles_n) * kVaeTile, m0 = ((int64_t)blockIdx.x / tiles_n) * kVaeTile;
-    const int64_t k_begin = (int64_t)blockIdx.z * kchunk, k_end = K < k_begin + kchunk ? K : k_begin + kchunk;
-    const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
-    float acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += kVaeTk) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = threadIdx.x + kVaeBlock * q;
-            const int kk = AK ? idx % kVaeTk : idx / kVaeTile, mm = AK ? idx / kVaeTk : idx % kVaeTile;
-            const int64_t gm = m0 + mm, gk = k0 + kk;
-            sA[kk][mm] = (gm < M && gk < k_end) ? A[gm * a_sm + gk * a_sk] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = threadIdx.x + kVaeBlock * q;
-            const int kk = BK ? idx % kVaeTk : idx / kVaeTile, nn = BK ? idx / kVaeTk : idx % kVaeTile;
-            const int64_t gn = n0 + nn, gk = k0 + kk;
-            sB[kk][nn] = (gn < N && gk < k_end) ? B[gk * b_sk + gn * b_sn] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < kVaeTk; ++kk) {
-            float a[4], b[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                a[q] = sA[kk][ty * 4 + q];
-                b[q] = sB[kk][tx * 4 + q];
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[p][q] = fmaf(a[p], b[q], acc[p][q]);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int64_t gm = m0 + ty * 4 + p;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t gn = n0 + tx * 4 + q;
-            if (gm >= M || gn >= N) continue;
-            if (EPI == 0) C[gm * N + gn] = acc[p][q] + bias[gn];
-            else if (EPI == 1) C[((int64_t)blockIdx.z * M + gm) * N + gn] = acc[p][q];
-            else vae_adam(C, am, av, gm * N + gn, acc[p][q], ad);
-        }
-    }
-}
-
 // ---- likelihood: one workgroup per row of the logits --------------------------------------------------------------------------
 // train != 0: row <- dL/do (divided by the batch's size), loss[u] = beta KL - LL.  train == 0: row <- p.
 __global__ __launch_bounds__(kVaeBlock) void vae_likelihood_kernel(
@@ -220,14 +126,14 @@ __global__ __launch_bounds__(kVaeBlock) void vae_likelihood_kernel(
     if (lik == LIK_MULT) {
         float mx = -INFINITY;
         for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) mx = fmaxf(mx, row[i]);
-        mx = vae_block_max(mx, sh);
+        mx = block_max(mx, sh);
         float se = 0.f;
         for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) {
             const float e = expf(row[i] - mx);
             row[i] = e;
             se += e;
         }
-        se = vae_block_sum(se, sh);   // (its barriers also order the stores of e before the reads below)
+        se = block_sum(se, sh);   // (its barriers also order the stores of e before the reads below)
         for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) row[i] = row[i] / se;
         __syncthreads();
         if (!train) return;
@@ -237,8 +143,8 @@ __global__ __launch_bounds__(kVaeBlock) void vae_likelihood_kernel(
             ll += logf(p + kVaeEps);
             s += -p / (p + kVaeEps);
         }
-        s = vae_block_sum(s, sh);
-        ll = vae_block_sum(ll, sh);
+        s = block_sum(s, sh);
+        ll = block_sum(ll, sh);
         for (int64_t i = threadIdx.x; i < I; i += kVaeBlock) {
             const float p = row[i];
             const float g = vae_holds(row_idx, lo, hi, (int32_t)i) ? -1.f / (p + kVaeEps) : 0.f;
@@ -264,7 +170,7 @@ __global__ __launch_bounds__(kVaeBlock) void vae_likelihood_kernel(
             row[i] = g * p * (1.f - p) * inv_b;
         }
         if (!train) return;
-        ll = vae_block_sum(ll, sh);
+        ll = block_sum(ll, sh);
     }
     if (threadIdx.x == 0) loss[u] = beta * kl[b] - ll;
 }
@@ -333,24 +239,6 @@ __global__ void vae_small_adam_kernel(float *w, float *am, float *av, VaeLayout 
     vae_adam(w, am, av, at, g, ad);
 }
 
-// ---- Adam on W1 (one row per item): the gradient of row i is the sum of ga1[b] over the batch's users that hold i ------------------
-__global__ void vae_w1_adam_kernel(float *w, float *am, float *av, VaeLayout L, int64_t I, int h, int64_t u0, int64_t nb,
-                                   const int64_t *__restrict__ col_ptr, const int32_t *__restrict__ col_idx,
-                                   const float *__restrict__ ga1, VaeAdam ad) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= I * h) return;
-    const int64_t i = e / h, j = e % h;
-    int64_t lo = col_ptr[i], hi = col_ptr[i + 1];
-    const int64_t end = hi;
-    while (lo < hi) {   // the first of the item's users that is not below u0
-        const int64_t mid = (lo + hi) >> 1;
-        if (col_idx[mid] < u0) lo = mid + 1; else hi = mid;
-    }
-    float g = 0.f;
-    for (; lo < end && col_idx[lo] < u0 + nb; ++lo) g += ga1[((int64_t)col_idx[lo] - u0) * h + j];
-    vae_adam(w, am, av, L.W1 + e, g, ad);
-}
-
 __global__ void vae_c1_adam_kernel(float *w, float *am, float *av, VaeLayout L, int64_t I, int64_t nb, const float *__restrict__ go,
                                    VaeAdam ad) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -358,11 +246,6 @@ __global__ void vae_c1_adam_kernel(float *w, float *am, float *av, VaeLayout L, 
     float g = 0.f;
     for (int64_t b = 0; b < nb; ++b) g += go[b * I + i];
     vae_adam(w, am, av, L.c1 + i, g, ad);
-}
-
-__global__ void vae_gather_pairs_kernel(const float *__restrict__ p, int64_t I, const int32_t *__restrict__ items, int64_t n, float *out) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < n) out[q] = p[q * I + items[q]];
 }
 
 }  // namespace
@@ -447,38 +330,15 @@ int cornac_hip_vaecf_destroy(cornac_hip_vaecf_t h) { return destroy_handle(h); }
 static void vae_put(cornac_hip_vaecf_t h, DevBuf<float> &buf, const float *const *tables) {
     int64_t off[10], rows[10], cols[10];
     vae_table_dims(h, off, rows, cols);
-    std::vector<float> w1t;
-    for (int q = 0; q < 10; ++q) {
-        if (!tables || !tables[q]) continue;
-        const float *src = tables[q];
-        if (q == 0) {
-            w1t.resize((size_t)(rows[0] * cols[0]));
-            for (int64_t j = 0; j < rows[0]; ++j)
-                for (int64_t i = 0; i < cols[0]; ++i) w1t[(size_t)(i * rows[0] + j)] = src[j * cols[0] + i];
-            src = w1t.data();
-        }
-        HIP_CHECK(hipMemcpyAsync(buf.p + off[q], src, (size_t)(rows[q] * cols[q]) * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < 10; ++q)
+        if (tables[q]) put_table(h->stream, buf.p + off[q], tables[q], rows[q], cols[q], q == 0);
 }
 
 static void vae_get(cornac_hip_vaecf_t h, const DevBuf<float> &buf, float *const *tables) {
     int64_t off[10], rows[10], cols[10];
     vae_table_dims(h, off, rows, cols);
-    for (int q = 0; q < 10; ++q) {
-        if (!tables || !tables[q]) continue;
-        const size_t n = (size_t)(rows[q] * cols[q]);
-        if (q == 0) {
-            std::vector<float> w1t(n);
-            HIP_CHECK(hipMemcpyAsync(w1t.data(), buf.p + off[q], n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            for (int64_t j = 0; j < rows[0]; ++j)
-                for (int64_t i = 0; i < cols[0]; ++i) tables[0][j * cols[0] + i] = w1t[(size_t)(i * rows[0] + j)];
-        } else {
-            HIP_CHECK(hipMemcpyAsync(tables[q], buf.p + off[q], n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        }
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < 10; ++q)
+        if (tables[q]) get_table(h->stream, buf.p + off[q], tables[q], rows[q], cols[q], q == 0);
 }
 
 int cornac_hip_vaecf_set_params(cornac_hip_vaecf_t h, const float *const *tables) {
@@ -516,19 +376,9 @@ int cornac_hip_vaecf_reset_optimizer(cornac_hip_vaecf_t h) {
     });
 }
 
-static unsigned vae_grid(int64_t n) { return (unsigned)((n + kVaeBlock - 1) / kVaeBlock); }
-
-static unsigned vae_tiles(int64_t M, int64_t N) {
-    const int64_t t = ((M + kVaeTile - 1) / kVaeTile) * ((N + kVaeTile - 1) / kVaeTile);
-    REQUIRE(t < (1ll << 31), "VAECF: %lld x %lld is more than a product's grid holds", (long long)M, (long long)N);
-    return (unsigned)t;
-}
-
 // h2 of nb rows -> logits[nb x I]
 static void vae_logits(cornac_hip_vaecf_t h, int64_t nb) {
-    const int64_t I = h->n_items, hh = h->h;
-    vae_gemm_kernel<true, true, 0><<<dim3(vae_tiles(nb, I)), kVaeBlock, 0, h->stream>>>(
-        h->h2.p, hh, 1, h->w.p + h->L.D1, 1, hh, nb, I, hh, hh + kVaeTk, h->logits.p, h->w.p + h->L.c1, nullptr, nullptr, VaeAdam{});
+    linear(h->stream, "VAECF", h->h2.p, h->w.p + h->L.D1, h->w.p + h->L.c1, nullptr, nb, h->n_items, h->h, h->logits.p);
 }
 
 int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float lr, float beta, const float *eps, uint64_t seed,
@@ -541,7 +391,7 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
         const int64_t nu = h->n_users, I = h->n_items, hh = h->h, k = h->k;
         vae_ensure(h, std::min(batch_size, nu));
         if (eps) h->eps.upload(eps, (size_t)(nu * k), h->stream);
-        else vae_noise_kernel<<<vae_grid(nu * k), kVaeBlock, 0, h->stream>>>(h->eps.p, nu, (int)k, batch_size, h->t, seed);
+        else vae_noise_kernel<<<grid(nu * k), kVaeBlock, 0, h->stream>>>(h->eps.p, nu, (int)k, batch_size, h->t, seed);
         float *w = h->w.p, *am = h->m.p, *av = h->v.p;
         const VaeLayout L = h->L;
         const int64_t small = 3 * hh * k + 2 * hh + 2 * k;
@@ -550,8 +400,7 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
             const int64_t u0 = s * batch_size, nb = std::min(batch_size, nu - u0);
             const float inv_b = 1.0f / (float)nb;
             h->t += 1;
-            const double bc1 = 1.0 - std::pow(0.9, (double)h->t), bc2 = 1.0 - std::pow(0.999, (double)h->t);
-            const VaeAdam ad{(float)(1.0 - 0.9), 0.999f, (float)(1.0 - 0.999), (float)((double)lr / bc1), (float)std::sqrt(bc2), 1e-8f};
+            const VaeAdam ad = adam_at(h->t, lr);
             vae_encode_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, nullptr, u0, w, L, (int)hh, (int)k, h->act,
                                                                         h->eps.p, h->h1.p, h->d1.p, h->mu.p, h->sd.p, h->z.p, h->h2.p,
                                                                         h->d2.p, h->kl.p);
@@ -559,19 +408,17 @@ int cornac_hip_vaecf_fit_epoch(cornac_hip_vaecf_t h, int64_t batch_size, float l
             vae_likelihood_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->rows.ptr.p, h->rows.idx.p, nullptr, u0, h->logits.p, I, h->lik, 1,
                                                                             inv_b, beta, h->kl.p, h->loss.p);
             // gh2 partials: go[nb x I] D1[I x h] over n_split item ranges
-            vae_gemm_kernel<true, false, 1><<<dim3(vae_tiles(nb, hh), 1, (unsigned)h->n_split), kVaeBlock, 0, h->stream>>>(
-                h->logits.p, I, 1, w + L.D1, hh, 1, nb, hh, I, h->kchunk, h->part.p, nullptr, nullptr, nullptr, VaeAdam{});
+            linear_back_split(h->stream, "VAECF", h->logits.p, w + L.D1, nb, hh, I, h->kchunk, h->n_split, h->part.p);
             vae_middle_kernel<<<(unsigned)nb, kVaeBlock, 0, h->stream>>>(h->part.p, h->n_split, nb, u0, w, L, (int)hh, (int)k, beta, inv_b,
                                                                         h->eps.p, h->d1.p, h->d2.p, h->mu.p, h->sd.p, h->ga2.p, h->gmu.p,
                                                                         h->glv.p, h->ga1.p);
-            vae_small_adam_kernel<<<vae_grid(small), kVaeBlock, 0, h->stream>>>(w, am, av, L, (int)hh, (int)k, nb, h->ga2.p, h->z.p, h->gmu.p,
-                                                                               h->glv.p, h->h1.p, h->ga1.p, ad);
-            vae_w1_adam_kernel<<<vae_grid(I * hh), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, (int)hh, u0, nb, h->cols.ptr.p, h->cols.idx.p,
-                                                                             h->ga1.p, ad);
-            vae_c1_adam_kernel<<<vae_grid(I), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, nb, h->logits.p, ad);
+            vae_small_adam_kernel<<<grid(small), kVaeBlock, 0, h->stream>>>(w, am, av, L, (int)hh, (int)k, nb, h->ga2.p, h->z.p, h->gmu.p,
+                                                                            h->glv.p, h->h1.p, h->ga1.p, ad);
+            vae_w1_adam_kernel<<<grid(I * hh), kVaeBlock, 0, h->stream>>>(w, am, av, L.W1, I, (int)hh, u0, nb, h->cols.ptr.p, h->cols.idx.p,
+                                                                          h->ga1.p, ad);
+            vae_c1_adam_kernel<<<grid(I), kVaeBlock, 0, h->stream>>>(w, am, av, L, I, nb, h->logits.p, ad);
             // D1: (go^T h2)[I x h], each tile applied at once
-            vae_gemm_kernel<false, false, 2><<<dim3(vae_tiles(I, hh)), kVaeBlock, 0, h->stream>>>(
-                h->logits.p, 1, I, h->h2.p, hh, 1, I, hh, nb, nb + kVaeTk, w + L.D1, nullptr, am + L.D1, av + L.D1, ad);
+            weight_adam(h->stream, "VAECF", h->logits.p, h->h2.p, nb, I, hh, w + L.D1, am + L.D1, av + L.D1, ad);
             HIP_CHECK(hipGetLastError());
         }
         std::vector<float> loss((size_t)nu);
@@ -613,7 +460,7 @@ static void vae_predict(cornac_hip_vaecf_t h, const int32_t *users, const int32_
         if (what == 1) {
             h->logits.download(out + b0 * I, (size_t)(nb * I), h->stream);
         } else {
-            vae_gather_pairs_kernel<<<vae_grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->item_ids.p, nb, h->out.p);
+            gather_pairs_kernel<<<grid(nb), kVaeBlock, 0, h->stream>>>(h->logits.p, I, h->item_ids.p, nb, h->out.p);
             h->out.download(out + b0, (size_t)nb, h->stream);
         }
     });
