@@ -1405,11 +1405,54 @@ class EaseModel(_HandleOwner):
         return _score_by_ids("cornac_hip_ease_score_pairs", self.h, np.float64, users, items)
 
 
-class VaecfModel(_HandleOwner):
+class _TableModel(_HandleOwner):
+    """Owner of a handle whose parameters are named float32 tables: set_params / get_params / get_state / reset_optimizer over
+    the library's `_PREFIX` + those names.  __init__ leaves `names` (the reference's state_dict order, which is the order of
+    the native pointer list) and `_shapes` (name -> shape)."""
+    _PREFIX = None     # "cornac_hip_vaecf_", ...
+    _STATEFUL = None   # the names that have optimiser state, in the native order (None: all of `names`)
+    _COUNTERS = 1      # the step counters that get_state returns after its two dicts
+    _DESTROY = property(lambda self: self._PREFIX + "destroy")
+
+    def _call(self, what, *args):
+        check(getattr(lib(), self._PREFIX + what)(getattr(self, self._HANDLE), *args))
+
+    def _empty(self, names=None):
+        return {n: np.empty(self._shapes[n], np.float32) for n in (self.names if names is None else names)}
+
+    def _pointers(self, tables, names=None):
+        """the native arguments of a dict of tables; a missing name skips"""
+        names = self.names if names is None else names
+        return ((_vp * len(names))(*[None if tables.get(n) is None else tables[n].ctypes.data for n in names]),)
+
+    def set_params(self, params):
+        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
+        for n, a in tables.items():
+            assert a.shape == self._shapes[n], "%s is %r, not %r" % (n, a.shape, self._shapes[n])
+        self._call("set_params", *self._pointers(tables))
+
+    def get_params(self):
+        out = self._empty()
+        self._call("get_params", *self._pointers(out))
+        return out
+
+    def get_state(self):
+        """(two dicts of the optimiser's state per stateful table, the step counters)"""
+        names = self._STATEFUL or self.names
+        a, b, t = self._empty(names), self._empty(names), [C.c_int64() for _ in range(self._COUNTERS)]
+        self._call("get_state", *self._pointers(a, names), *self._pointers(b, names), *[C.byref(c) for c in t])
+        return (a, b) + tuple(int(c.value) for c in t)
+
+    def reset_optimizer(self):
+        self._call("reset_optimizer")
+
+
+class VaecfModel(_TableModel):
     """Owner of a cornac_hip_vaecf_t handle: the binarised training rows, the ten tables of the reference's VAE
     (cornac/models/vaecf/vaecf.py:37-64) with Adam's moments and step counter, the epoch of vaecf.py:127-144 and the scores
-    of recom_vaecf.py:193-202.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
-    _DESTROY = "cornac_hip_vaecf_destroy"
+    of recom_vaecf.py:193-202.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes.
+    get_state() is (m, v, t): Adam's exp_avg and exp_avg_sq per table, and its step counter."""
+    _PREFIX = "cornac_hip_vaecf_"
     _HANDLE = "h_"   # (`h` is the hidden size here)
     NAMES = ("encoder.fc0.weight", "encoder.fc0.bias", "enc_mu.weight", "enc_mu.bias", "enc_logvar.weight", "enc_logvar.bias",
              "decoder.fc0.weight", "decoder.fc0.bias", "decoder.fc1.weight", "decoder.fc1.bias")
@@ -1423,38 +1466,11 @@ class VaecfModel(_HandleOwner):
     def __init__(self, X, k, h, act_fn="tanh", likelihood="mult", device=0):
         self.n_users, self.n_items = (int(x) for x in X.shape)
         self.k, self.h = int(k), int(h)
+        self.names, self._shapes = self.NAMES, self.shapes(self.n_items, self.k, self.h)
         indptr, indices, _ = _csr_arrays(X)
         self.h_ = _vp()
         check(lib().cornac_hip_vaecf_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                             self.k, self.h, self.ACTS.index(act_fn), self.LIKELIHOODS.index(likelihood)))
-
-    def _empty(self):
-        sh = self.shapes(self.n_items, self.k, self.h)
-        return {n: np.empty(sh[n], np.float32) for n in self.NAMES}
-
-    def _pointers(self, tables):
-        return (_vp * 10)(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.NAMES])
-
-    def set_params(self, params):
-        sh = self.shapes(self.n_items, self.k, self.h)
-        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
-        for n, a in tables.items():
-            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
-        check(lib().cornac_hip_vaecf_set_params(self.h_, self._pointers(tables)))
-
-    def get_params(self):
-        out = self._empty()
-        check(lib().cornac_hip_vaecf_get_params(self.h_, self._pointers(out)))
-        return out
-
-    def get_state(self):
-        """(m, v, t): Adam's exp_avg and exp_avg_sq per table, and its step counter"""
-        m, v, t = self._empty(), self._empty(), C.c_int64()
-        check(lib().cornac_hip_vaecf_get_state(self.h_, self._pointers(m), self._pointers(v), C.byref(t)))
-        return m, v, int(t.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_vaecf_reset_optimizer(self.h_))
 
     def fit_epoch(self, batch_size, lr, beta, eps=None, seed=0):
         """one epoch; eps [n_users, k] is the noise (None: the device generator under `seed`).  Returns (the sum of the
@@ -1480,19 +1496,21 @@ class VaecfModel(_HandleOwner):
         return _score_by_ids("cornac_hip_vaecf_score_pairs", self.h_, np.float32, users, items)
 
 
-class RecvaeModel(_HandleOwner):
+class RecvaeModel(_TableModel):
     """Owner of a cornac_hip_recvae_t handle: the training rows with their values, the 53 tables of the reference's VAE
     (cornac/models/recvae/recvae.py:78-84: encoder, prior tables, old encoder, decoder) with the two Adams' moments and step
     counters, the pass of recom_recvae.py:131-145, update_prior (recvae.py:116-117) and the scores of recom_recvae.py:241-278
-    in evaluation mode.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
-    _DESTROY = "cornac_hip_recvae_destroy"
+    in evaluation mode.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes.
+    get_state() is (m, v, t_enc, t_dec): Adam's exp_avg and exp_avg_sq per trainable table, and the two step counters."""
+    _PREFIX = "cornac_hip_recvae_"
     _HANDLE = "h_"
+    _COUNTERS = 2
     ENCODER = tuple("%s%d.%s" % (kind, l, p) for l in range(1, 6) for kind in ("fc", "ln") for p in ("weight", "bias")) + (
         "fc_mu.weight", "fc_mu.bias", "fc_logvar.weight", "fc_logvar.bias")
     PRIORS = ("prior.mu_prior", "prior.logvar_prior", "prior.logvar_uniform_prior")
     NAMES = tuple("encoder." + n for n in ENCODER) + PRIORS + tuple("prior.encoder_old." + n for n in ENCODER) + (
         "decoder.weight", "decoder.bias")
-    TRAINABLE = tuple("encoder." + n for n in ENCODER) + ("decoder.weight", "decoder.bias")
+    TRAINABLE = _STATEFUL = tuple("encoder." + n for n in ENCODER) + ("decoder.weight", "decoder.bias")
     MAX_HIDDEN, MAX_LATENT, MAX_BATCH = 1024, 256, 1024
 
     @staticmethod
@@ -1505,41 +1523,12 @@ class RecvaeModel(_HandleOwner):
     def __init__(self, X, hidden, latent, device=0):
         self.n_users, self.n_items = (int(x) for x in X.shape)
         self.hidden, self.latent = int(hidden), int(latent)
+        self.names, self._shapes = self.NAMES, self.shapes(self.n_items, self.hidden, self.latent)
         indptr, indices, data = _csr_arrays(X)
         self.nnz = len(indices)
         self.h_ = _vp()
         check(lib().cornac_hip_recvae_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                              _ptr(data), self.hidden, self.latent))
-
-    def _empty(self, names):
-        sh = self.shapes(self.n_items, self.hidden, self.latent)
-        return {n: np.empty(sh[n], np.float32) for n in names}
-
-    @staticmethod
-    def _pointers(tables, names):
-        return (_vp * len(names))(*[None if tables.get(n) is None else tables[n].ctypes.data for n in names])
-
-    def set_params(self, params):
-        sh = self.shapes(self.n_items, self.hidden, self.latent)
-        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
-        for n, a in tables.items():
-            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
-        check(lib().cornac_hip_recvae_set_params(self.h_, self._pointers(tables, self.NAMES)))
-
-    def get_params(self):
-        out = self._empty(self.NAMES)
-        check(lib().cornac_hip_recvae_get_params(self.h_, self._pointers(out, self.NAMES)))
-        return out
-
-    def get_state(self):
-        """(m, v, t_enc, t_dec): Adam's exp_avg and exp_avg_sq per trainable table, and the two step counters"""
-        m, v, te, td = self._empty(self.TRAINABLE), self._empty(self.TRAINABLE), C.c_int64(), C.c_int64()
-        check(lib().cornac_hip_recvae_get_state(self.h_, self._pointers(m, self.TRAINABLE), self._pointers(v, self.TRAINABLE),
-                                                C.byref(te), C.byref(td)))
-        return m, v, int(te.value), int(td.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_recvae_reset_optimizer(self.h_))
 
     def update_prior(self):
         check(lib().cornac_hip_recvae_update_prior(self.h_))
@@ -1586,13 +1575,15 @@ class RecvaeModel(_HandleOwner):
 BIVAE_RANGE = 512   # CORNAC_HIP_BIVAE_RANGE: rows of the other side's table per workgroup of the fused decode's dense pass
 
 
-class BivaeModel(_HandleOwner):
+class BivaeModel(_TableModel):
     """Owner of a cornac_hip_bivae_t handle: the binarised training matrix in both orientations, the 12 tables of the
     reference's BiVAE (cornac/models/bivaecf/bivae.py:66-86) with Adam's moments and the two step counters, the factor tables
     theta, beta, mu_theta, mu_beta (bivae.py:48-53), the epoch of bivae.py:194-256, the final passes of :258-274 and the
-    scores of recom_bivaecf.py:217-224.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes."""
-    _DESTROY = "cornac_hip_bivae_destroy"
+    scores of recom_bivaecf.py:217-224.  Tables travel as dicts keyed by the reference's state_dict names, in its shapes.
+    get_state() is (m, v, t_user, t_item): Adam's exp_avg and exp_avg_sq per table, and the two optimisers' step counters."""
+    _PREFIX = "cornac_hip_bivae_"
     _HANDLE = "h_"   # (`h` is the hidden size here)
+    _COUNTERS = 2
     NAMES = ("user_encoder.fc0.weight", "user_encoder.fc0.bias", "user_mu.weight", "user_mu.bias", "user_std.weight",
              "user_std.bias", "item_encoder.fc0.weight", "item_encoder.fc0.bias", "item_mu.weight", "item_mu.bias",
              "item_std.weight", "item_std.bias")
@@ -1613,29 +1604,11 @@ class BivaeModel(_HandleOwner):
     def __init__(self, X, k, h, act_fn="tanh", likelihood="pois", device=0):
         self.n_users, self.n_items = (int(x) for x in X.shape)
         self.k, self.h = int(k), int(h)
+        self.names, self._shapes = self.NAMES, self.shapes(self.n_users, self.n_items, self.k, self.h)
         indptr, indices, _ = _csr_arrays(X)
         self.h_ = _vp()
         check(lib().cornac_hip_bivae_create(C.byref(self.h_), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                             self.k, self.h, self.ACTS.index(act_fn), self.LIKELIHOODS.index(likelihood)))
-
-    def _empty(self):
-        sh = self.shapes(self.n_users, self.n_items, self.k, self.h)
-        return {n: np.empty(sh[n], np.float32) for n in self.NAMES}
-
-    def _pointers(self, tables):
-        return (_vp * 12)(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.NAMES])
-
-    def set_params(self, params):
-        sh = self.shapes(self.n_users, self.n_items, self.k, self.h)
-        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
-        for n, a in tables.items():
-            assert a.shape == sh[n], "%s is %r, not %r" % (n, a.shape, sh[n])
-        check(lib().cornac_hip_bivae_set_params(self.h_, self._pointers(tables)))
-
-    def get_params(self):
-        out = self._empty()
-        check(lib().cornac_hip_bivae_get_params(self.h_, self._pointers(out)))
-        return out
 
     def set_factors(self, theta=None, beta=None, mu_theta=None, mu_beta=None):
         sh = self.factor_shapes(self.n_users, self.n_items, self.k)
@@ -1650,15 +1623,6 @@ class BivaeModel(_HandleOwner):
         out = {n: np.empty(sh[n], np.float32) for n in self.FACTORS}
         check(lib().cornac_hip_bivae_get_factors(self.h_, *[_ptr(out[n]) for n in self.FACTORS]))
         return out
-
-    def get_state(self):
-        """(m, v, t_user, t_item): Adam's exp_avg and exp_avg_sq per table, and the two optimisers' step counters"""
-        m, v, tu, ti = self._empty(), self._empty(), C.c_int64(), C.c_int64()
-        check(lib().cornac_hip_bivae_get_state(self.h_, self._pointers(m), self._pointers(v), C.byref(tu), C.byref(ti)))
-        return m, v, int(tu.value), int(ti.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_bivae_reset_optimizer(self.h_))
 
     def n_steps(self, batch_size):
         """(item steps, user steps) of an epoch"""
@@ -1699,12 +1663,13 @@ class BivaeModel(_HandleOwner):
         return _score_by_ids("cornac_hip_bivae_score_pairs", self.h_, np.float32, users, items)
 
 
-class NcfModel(_HandleOwner):
+class NcfModel(_TableModel):
     """Owner of a cornac_hip_ncf_t handle: the training CSR with its values, the tables of the reference's GMF / MLP / NeuMF
     module (cornac/models/ncf/backend_pt.py:22-175) with the learner's state and step counter, the epoch of
     recom_ncf_base.py:266-281 over given or device-drawn samples, and the scores of the three _score_pt.  Tables travel as
-    dicts keyed by the reference's state_dict names, in its shapes."""
-    _DESTROY = "cornac_hip_ncf_destroy"
+    dicts keyed by the reference's state_dict names, in its shapes.  get_state() is (s1, s2, t): adam's exp_avg and exp_avg_sq,
+    rmsprop's square_avg or adagrad's sum in s1, and the step counter."""
+    _PREFIX = "cornac_hip_ncf_"
     KINDS = ("GMF", "MLP", "NeuMF")
     ACTS = ("sigmoid", "tanh", "elu", "selu", "relu", "relu6", "leaky_relu")
     LEARNERS = ("adam", "sgd", "rmsprop", "adagrad")
@@ -1757,32 +1722,6 @@ class NcfModel(_HandleOwner):
         check(lib().cornac_hip_ncf_n_tables(self.h, C.byref(n)))
         assert n.value == len(self.names)
 
-    def _empty(self):
-        return {n: np.empty(self._shapes[n], np.float32) for n in self.names}
-
-    def _pointers(self, tables):
-        return (_vp * len(self.names))(*[None if tables.get(n) is None else tables[n].ctypes.data for n in self.names])
-
-    def set_params(self, params):
-        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
-        for n, a in tables.items():
-            assert a.shape == self._shapes[n], "%s is %r, not %r" % (n, a.shape, self._shapes[n])
-        check(lib().cornac_hip_ncf_set_params(self.h, self._pointers(tables)))
-
-    def get_params(self):
-        out = self._empty()
-        check(lib().cornac_hip_ncf_get_params(self.h, self._pointers(out)))
-        return out
-
-    def get_state(self):
-        """(s1, s2, t): adam's exp_avg and exp_avg_sq, rmsprop's square_avg or adagrad's sum in s1, and the step counter"""
-        s1, s2, t = self._empty(), self._empty(), C.c_int64()
-        check(lib().cornac_hip_ncf_get_state(self.h, self._pointers(s1), self._pointers(s2), C.byref(t)))
-        return s1, s2, int(t.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_ncf_reset_optimizer(self.h))
-
     def fit_epoch(self, step_ptr, users, items, labels, lr, reg=0.0, learner="adam"):
         """one epoch over the given samples, step s being [step_ptr[s], step_ptr[s + 1]).  Returns (the sum of the steps' mean
         losses, the per-step losses)."""
@@ -1825,11 +1764,11 @@ class NcfModel(_HandleOwner):
         return _score_by_ids("cornac_hip_ncf_score_pairs", self.h, np.float32, users, items)
 
 
-class LightGcnModel(_HandleOwner):
+class LightGcnModel(_TableModel):
     """Owner of a cornac_hip_lightgcn_t handle: the normalised adjacency of the train matrix's bipartite graph
     (cornac/models/lightgcn/lightgcn.py:13-41), the layer-0 tables `feature_dict.user` / `feature_dict.item` with Adam's state
     and step counter, the epoch of recom_lightgcn.py:157-179 over given triplets, and the final embeddings of model(graph)."""
-    _DESTROY = "cornac_hip_lightgcn_destroy"
+    _PREFIX = "cornac_hip_lightgcn_"
     PIECE = 512        # edges of one piece of a long row: rows above it are summed in pieces, combined in piece order
     MAX_STEP = 16384   # triplets of one step
     NAMES = ("user", "item")
@@ -1837,34 +1776,31 @@ class LightGcnModel(_HandleOwner):
     def __init__(self, X, emb_size=64, num_layers=3, device=0):
         self.n_users, self.n_items = (int(x) for x in X.shape)
         self.emb_size, self.num_layers = int(emb_size), int(num_layers)
+        self.names, self._shapes = self.NAMES, {"user": (self.n_users, self.emb_size), "item": (self.n_items, self.emb_size)}
         indptr, indices, _ = _csr_arrays(X)
         self.nnz = int(indptr[-1])
         self.h = _vp()
         check(lib().cornac_hip_lightgcn_create(C.byref(self.h), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                                self.emb_size, self.num_layers))
 
-    def _empty(self):
-        return np.empty((self.n_users, self.emb_size), np.float32), np.empty((self.n_items, self.emb_size), np.float32)
+    def _pointers(self, tables, names=None):
+        """(user, item): the native calls take the two tables as arguments of their own"""
+        return tuple(_ptr(tables.get(n)) for n in self.NAMES)
 
     def set_params(self, user=None, item=None):
         user, item = _f32c(user), _f32c(item)
-        assert user is None or user.shape == (self.n_users, self.emb_size), "user is %r" % (user.shape,)
-        assert item is None or item.shape == (self.n_items, self.emb_size), "item is %r" % (item.shape,)
-        check(lib().cornac_hip_lightgcn_set_params(self.h, _ptr(user), _ptr(item)))
+        assert user is None or user.shape == self._shapes["user"], "user is %r" % (user.shape,)
+        assert item is None or item.shape == self._shapes["item"], "item is %r" % (item.shape,)
+        self._call("set_params", _ptr(user), _ptr(item))
 
     def get_params(self):
-        user, item = self._empty()
-        check(lib().cornac_hip_lightgcn_get_params(self.h, _ptr(user), _ptr(item)))
-        return user, item
+        out = super().get_params()
+        return out["user"], out["item"]
 
     def get_state(self):
         """(m_user, m_item, v_user, v_item, t): Adam's exp_avg and exp_avg_sq and its step counter"""
-        (mu, mi), (vu, vi), t = self._empty(), self._empty(), C.c_int64()
-        check(lib().cornac_hip_lightgcn_get_state(self.h, _ptr(mu), _ptr(mi), _ptr(vu), _ptr(vi), C.byref(t)))
-        return mu, mi, vu, vi, int(t.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_lightgcn_reset_optimizer(self.h))
+        m, v, t = super().get_state()
+        return m["user"], m["item"], v["user"], v["item"], t
 
     def fit_epoch(self, step_ptr, users, pos, neg, lr, lambda_reg):
         """one epoch over the given triplets, step s being [step_ptr[s], step_ptr[s + 1]).  Returns the per-step (losses, bpr,
@@ -1879,17 +1815,18 @@ class LightGcnModel(_HandleOwner):
 
     def propagate(self):
         """(U, V): the final embeddings, the mean of the layers' tables"""
-        user, item = self._empty()
-        check(lib().cornac_hip_lightgcn_propagate(self.h, _ptr(user), _ptr(item)))
-        return user, item
+        out = self._empty()
+        self._call("propagate", *self._pointers(out))
+        return out["user"], out["item"]
 
 
-class NgcfModel(_HandleOwner):
+class NgcfModel(_TableModel):
     """Owner of a cornac_hip_ngcf_t handle: the graph of cornac/models/ngcf/ngcf.py:14-37 with its edge norms, the tables
     `feature_dict.user` / `feature_dict.item` and every layer's W1 / W2 with Adam's state and step counter, the train-mode epoch
     of recom_ngcf.py:159-184 over given triplets, and the concatenated embeddings of the eval-mode model(graph).  Parameters
-    travel as dicts under the reference's state_dict names, in its order (`names`)."""
-    _DESTROY = "cornac_hip_ngcf_destroy"
+    travel as dicts under the reference's state_dict names, in its order (`names`).  get_state() is (m, v, t): Adam's exp_avg
+    and exp_avg_sq as dicts like get_params', and its step counter."""
+    _PREFIX = "cornac_hip_ngcf_"
     PIECE = 512          # edges of one piece of a long row (the hop is LightGCN's)
     MAX_STEP = 16384     # triplets of one step
     WGRAD_ROWS = 2048    # rows of one chunk of the weight and bias gradients; the chunks' partials are added in chunk order
@@ -1916,7 +1853,7 @@ class NgcfModel(_HandleOwner):
         assert len(self.layer_sizes) == len(self.dropout_rates), "'layer_sizes' and 'dropout_rates' must be of the same size"
         self.dropout_key = int(dropout_key) & 0xFFFFFFFFFFFFFFFF
         self.D = self.emb_size + sum(self.layer_sizes)
-        self.shapes = self.param_shapes(self.n_users, self.n_items, self.emb_size, self.layer_sizes)
+        self.shapes = self._shapes = self.param_shapes(self.n_users, self.n_items, self.emb_size, self.layer_sizes)
         self.names = list(self.shapes)
         indptr, indices, _ = _csr_arrays(X)
         self.nnz = int(indptr[-1])
@@ -1925,37 +1862,17 @@ class NgcfModel(_HandleOwner):
         check(lib().cornac_hip_ngcf_create(C.byref(self.h), device, self.n_users, self.n_items, _ptr(indptr), _ptr(indices),
                                            self.emb_size, len(sizes), _ptr(sizes), _ptr(rates), self.dropout_key))
 
-    def _empty(self):
+    def _empty(self, names=None):
         from collections import OrderedDict
 
-        return OrderedDict((n, np.empty(s, np.float32)) for n, s in self.shapes.items())
+        return OrderedDict(super()._empty(names))
 
-    def _args(self, tables):
-        """(user, item, layers[4 L]) pointers of a dict of tables; a missing name skips"""
+    def _pointers(self, tables, names=None):
+        """(user, item, layers[4 L]): the native calls take the two embedding tables as arguments of their own"""
         at = lambda n: None if tables.get(n) is None else tables[n].ctypes.data   # noqa: E731
         layers = (_vp * (4 * len(self.layer_sizes)))(*[at("layers.%d.%s" % (l, s)) for l in range(len(self.layer_sizes))
                                                        for s in ("W1.weight", "W1.bias", "W2.weight", "W2.bias")])
         return at("feature_dict.user"), at("feature_dict.item"), layers
-
-    def set_params(self, params):
-        tables = {n: np.ascontiguousarray(a, np.float32) for n, a in params.items() if a is not None}
-        for n, a in tables.items():
-            assert a.shape == self.shapes[n], "%s is %r, not %r" % (n, a.shape, self.shapes[n])
-        check(lib().cornac_hip_ngcf_set_params(self.h, *self._args(tables)))
-
-    def get_params(self):
-        out = self._empty()
-        check(lib().cornac_hip_ngcf_get_params(self.h, *self._args(out)))
-        return out
-
-    def get_state(self):
-        """(m, v, t): Adam's exp_avg and exp_avg_sq as dicts like get_params', and its step counter"""
-        m, v, t = self._empty(), self._empty(), C.c_int64()
-        check(lib().cornac_hip_ngcf_get_state(self.h, *(self._args(m) + self._args(v) + (C.byref(t),))))
-        return m, v, int(t.value)
-
-    def reset_optimizer(self):
-        check(lib().cornac_hip_ngcf_reset_optimizer(self.h))
 
     def fit_epoch(self, step_ptr, users, pos, neg, lr, lambda_reg):
         """one train-mode epoch over the given triplets, step s being [step_ptr[s], step_ptr[s + 1]).  Returns the per-step

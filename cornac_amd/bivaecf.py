@@ -23,7 +23,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint
+from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint, filled_handle, float32_tables
 
 NAMES = _lib.BivaeModel.NAMES
 FACTORS = _lib.BivaeModel.FACTORS
@@ -64,12 +64,7 @@ class BiVAETables:
         if set(state) != set(NAMES):
             raise KeyError("state_dict needs exactly the keys %r" % (NAMES,))
         old = self.tables
-        tabs = OrderedDict()
-        for n in NAMES:
-            a = state[n]
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
-        self.tables = tabs
+        self.tables = float32_tables(state, NAMES)
         try:
             self._check()
         except ValueError:
@@ -152,8 +147,7 @@ class BiVAECF(HandleScoredRecommender):
             self.bivae = self._initial_tables(n_users, n_items, k, h)
         model = _lib.BivaeModel(self.r_mat, k, h, self.act_fn, self.likelihood, device=self.device)
         try:
-            model.set_params(self.bivae.tables)
-            model.set_factors(**{n: getattr(self.bivae, n) for n in FACTORS})
+            self._fill(model)
             device_seed = int(np.random.SeedSequence().entropy % (1 << 63)) if self.seed is None else 0
             self.loss_history = []
             for epoch in range(int(self.n_epochs)):
@@ -192,10 +186,6 @@ class BiVAECF(HandleScoredRecommender):
     batch_num_items = Recommender.batch_num_items
     register_exclusions = Recommender.register_exclusions
 
-    def _drop_scorer(self):
-        HandleScoredRecommender._drop_scorer(self)
-        self.__dict__.pop("_rank_tables", None)
-
     def _handle_key(self):
         X = self.r_mat
         return (id(X),) + tuple(_table_fingerprint(a) for a in (X.indptr, X.indices)) + tuple(
@@ -203,13 +193,11 @@ class BiVAECF(HandleScoredRecommender):
 
     def _build_handle(self):
         model = _lib.BivaeModel(self.r_mat, self.k, self._check_structure(), self.act_fn, self.likelihood, device=self.device)
-        try:
-            model.set_params(self.bivae.tables)
-            model.set_factors(**{n: getattr(self.bivae, n) for n in FACTORS})
-        except Exception:
-            model.close()
-            raise
-        return model
+        return filled_handle(model, self._fill)
+
+    def _fill(self, model):
+        model.set_params(self.bivae.tables)
+        model.set_factors(**{n: getattr(self.bivae, n) for n in FACTORS})
 
     def _pair_values(self, handle, users, items):
         """recom_bivaecf.py:221-225: the pair's probability scaled from [0, 1] to [min_rating, max_rating]"""

@@ -337,6 +337,7 @@ struct BvSide {
     int64_t n = 0, N = 0;   // this side's ids; the other side's (W1's input width, and the decoder's table length)
     int64_t t = 0;          // this side's Adam step counter
     BvLayout L{};
+    std::vector<TableSlot> slots;   // this side's six tables of w / m / v in the reference's state_dict order
     const DevCsr *own = nullptr, *other = nullptr;   // this side's rows; the other orientation
     DevBuf<float> w, m, v, z, mu, eps, loss;         // z: theta or beta [n x k]; mu: mu_theta or mu_beta
 };
@@ -406,6 +407,9 @@ int cornac_hip_bivae_create(cornac_hip_bivae_t *out, int device, int64_t n_users
             BvLayout &L = d.L;
             L.W1 = 0; L.b1 = L.W1 + d.N * hh; L.Wm = L.b1 + hh; L.bm = L.Wm + kk * hh; L.Ws = L.bm + kk; L.bs = L.Ws + kk * hh;
             L.total = L.bs + kk;
+            // in the reference's shapes: fc0.weight is [h x N] there, [N x h] here
+            d.slots = {{L.W1, hh, d.N, true}, {L.b1, 1, hh, false}, {L.Wm, kk, hh, false},
+                       {L.bm, 1, kk, false}, {L.Ws, kk, hh, false}, {L.bs, 1, kk, false}};
             for (DevBuf<float> *b : {&d.w, &d.m, &d.v}) alloc_named(*b, (size_t)L.total, "BiVAECF", "the tables and Adam's moments");
             for (DevBuf<float> *b : {&d.z, &d.mu}) alloc_named(*b, (size_t)(d.n * kk), "BiVAECF", "the factor tables");
             alloc_named(d.eps, (size_t)(2 * d.n * kk), "BiVAECF", "the noise");
@@ -420,42 +424,20 @@ int cornac_hip_bivae_create(cornac_hip_bivae_t *out, int device, int64_t n_users
 
 int cornac_hip_bivae_destroy(cornac_hip_bivae_t h) { return destroy_handle(h); }
 
-// table q of the 12 (state_dict order: the user side's six, then the item side's): its side, offset and host shape
-static void bv_table(cornac_hip_bivae_t h, int q, BvSide **side, int64_t *off, int64_t *rows, int64_t *cols) {
-    BvSide &d = h->side[q < 6 ? SIDE_USER : SIDE_ITEM];
-    const BvLayout &L = d.L;
-    const int64_t hh = h->h, k = h->k;
-    const int64_t o[6] = {L.W1, L.b1, L.Wm, L.bm, L.Ws, L.bs}, r[6] = {hh, 1, k, 1, k, 1}, c[6] = {d.N, hh, hh, k, hh, k};
-    *side = &d; *off = o[q % 6]; *rows = r[q % 6]; *cols = c[q % 6];
+// host <-> device copies of the 12 tables of one kind (the buffer `buf` of a side): the user side's six, then the item side's
+static void bv_put(cornac_hip_bivae_t h, DevBuf<float> BvSide::*buf, const float *const *tables) {
+    for (int s = 0; s < 2; ++s) put_tables(h->stream, (h->side[s].*buf).p, h->side[s].slots, tables + 6 * s);
 }
 
-// host <-> device copies of the 12 tables of one kind (0 w, 1 m, 2 v), in the reference's shapes (fc0.weight is [h x N]
-// there, [N x h] here)
-static void bv_put(cornac_hip_bivae_t h, int kind, const float *const *tables) {
-    for (int q = 0; q < 12; ++q) {
-        if (!tables[q]) continue;
-        BvSide *d; int64_t off, rows, cols;
-        bv_table(h, q, &d, &off, &rows, &cols);
-        DevBuf<float> &buf = kind == 0 ? d->w : kind == 1 ? d->m : d->v;
-        put_table(h->stream, buf.p + off, tables[q], rows, cols, q % 6 == 0);
-    }
-}
-
-static void bv_get(cornac_hip_bivae_t h, int kind, float *const *tables) {
-    for (int q = 0; q < 12; ++q) {
-        if (!tables[q]) continue;
-        BvSide *d; int64_t off, rows, cols;
-        bv_table(h, q, &d, &off, &rows, &cols);
-        const DevBuf<float> &buf = kind == 0 ? d->w : kind == 1 ? d->m : d->v;
-        get_table(h->stream, buf.p + off, tables[q], rows, cols, q % 6 == 0);
-    }
+static void bv_get(cornac_hip_bivae_t h, DevBuf<float> BvSide::*buf, float *const *tables) {
+    for (int s = 0; s < 2; ++s) get_tables(h->stream, (h->side[s].*buf).p, h->side[s].slots, tables + 6 * s);
 }
 
 int cornac_hip_bivae_set_params(cornac_hip_bivae_t h, const float *const *tables) {
     return guarded([&] {
         check_handle(h, "BiVAECF handle");
         REQUIRE(tables != nullptr, "BiVAECF: tables is NULL");
-        bv_put(h, 0, tables);
+        bv_put(h, &BvSide::w, tables);
     });
 }
 
@@ -463,7 +445,7 @@ int cornac_hip_bivae_get_params(cornac_hip_bivae_t h, float *const *tables) {
     return guarded([&] {
         check_handle(h, "BiVAECF handle");
         REQUIRE(tables != nullptr, "BiVAECF: tables is NULL");
-        bv_get(h, 0, tables);
+        bv_get(h, &BvSide::w, tables);
     });
 }
 
@@ -494,8 +476,8 @@ int cornac_hip_bivae_get_factors(cornac_hip_bivae_t h, float *theta, float *beta
 int cornac_hip_bivae_get_state(cornac_hip_bivae_t h, float *const *m, float *const *v, int64_t *t_user, int64_t *t_item) {
     return guarded([&] {
         check_handle(h, "BiVAECF handle");
-        if (m) bv_get(h, 1, m);
-        if (v) bv_get(h, 2, v);
+        if (m) bv_get(h, &BvSide::m, m);
+        if (v) bv_get(h, &BvSide::v, v);
         if (t_user) *t_user = h->side[SIDE_USER].t;
         if (t_item) *t_item = h->side[SIDE_ITEM].t;
     });
@@ -504,12 +486,9 @@ int cornac_hip_bivae_get_state(cornac_hip_bivae_t h, float *const *m, float *con
 int cornac_hip_bivae_reset_optimizer(cornac_hip_bivae_t h) {
     return guarded([&] {
         check_handle(h, "BiVAECF handle");
-        for (BvSide &d : h->side) {
-            HIP_CHECK(hipMemsetAsync(d.m.p, 0, d.m.n * sizeof(float), h->stream));
-            HIP_CHECK(hipMemsetAsync(d.v.p, 0, d.v.n * sizeof(float), h->stream));
-            d.t = 0;
-        }
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        BvSide &u = h->side[SIDE_USER], &i = h->side[SIDE_ITEM];
+        zero_state(h->stream, {&u.m, &u.v, &i.m, &i.v});
+        u.t = i.t = 0;
     });
 }
 

@@ -60,6 +60,7 @@ struct cornac_hip_lightgcn : ModelHandle {
     int d = 0, L = 0;
     int64_t t = 0;   // Adam's step counter
     DevBuf<float> w, m, v;          // [E0_user | E0_item] and Adam's state
+    std::vector<TableSlot> slots;   // the two tables of w / m / v / E
     DevBuf<float> E, Gr, gs, ha, hb;   // final embeddings, gradient at them, P(gradient), the hops' ping-pong
     LgcnEpoch ep;                   // an epoch's triplets
 };
@@ -95,6 +96,7 @@ int cornac_hip_lightgcn_create(cornac_hip_lightgcn_t *out, int device, int64_t n
         h->n_users = n_users; h->n_items = n_items;
         h->d = emb_size; h->L = num_layers;
         h->total = h->g.n_nodes * emb_size;
+        h->slots = {{0, n_users, emb_size, false}, {n_users * emb_size, n_items, emb_size, false}};
         h->open(device);
         h->g.upload(nm, emb_size, h->stream);
         for (DevBuf<float> *b : {&h->w, &h->m, &h->v, &h->E, &h->Gr, &h->gs, &h->ha, &h->hb}) {
@@ -109,24 +111,16 @@ int cornac_hip_lightgcn_create(cornac_hip_lightgcn_t *out, int device, int64_t n
 
 int cornac_hip_lightgcn_destroy(cornac_hip_lightgcn_t h) { return destroy_handle(h); }
 
-static void lgcn_put(cornac_hip_lightgcn_t h, DevBuf<float> &buf, const float *user, const float *item) {
-    const size_t nu = (size_t)(h->n_users * h->d), ni = (size_t)(h->n_items * h->d);
-    if (user) HIP_CHECK(hipMemcpyAsync(buf.p, user, nu * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (item) HIP_CHECK(hipMemcpyAsync(buf.p + nu, item, ni * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
 static void lgcn_get(cornac_hip_lightgcn_t h, const DevBuf<float> &buf, float *user, float *item) {
-    const size_t nu = (size_t)(h->n_users * h->d), ni = (size_t)(h->n_items * h->d);
-    if (user) HIP_CHECK(hipMemcpyAsync(user, buf.p, nu * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (item) HIP_CHECK(hipMemcpyAsync(item, buf.p + nu, ni * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    float *const tables[2] = {user, item};
+    get_tables(h->stream, buf.p, h->slots, tables);
 }
 
 int cornac_hip_lightgcn_set_params(cornac_hip_lightgcn_t h, const float *user, const float *item) {
     return guarded([&] {
         check_handle(h, "lightgcn handle");
-        lgcn_put(h, h->w, user, item);
+        const float *const tables[2] = {user, item};
+        put_tables(h->stream, h->w.p, h->slots, tables);
     });
 }
 
@@ -149,9 +143,7 @@ int cornac_hip_lightgcn_get_state(cornac_hip_lightgcn_t h, float *m_user, float 
 int cornac_hip_lightgcn_reset_optimizer(cornac_hip_lightgcn_t h) {
     return guarded([&] {
         check_handle(h, "lightgcn handle");
-        HIP_CHECK(hipMemsetAsync(h->m.p, 0, h->m.n * sizeof(float), h->stream));
-        HIP_CHECK(hipMemsetAsync(h->v.p, 0, h->v.n * sizeof(float), h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        zero_state(h->stream, {&h->m, &h->v});
         h->t = 0;
     });
 }

@@ -440,6 +440,7 @@ struct cornac_hip_ncf : ModelHandle {
     int64_t n_users = 0, n_items = 0, nnz = 0;
     NcfNet N{};
     NcfTables all{}, emb{}, small{};   // every table in state_dict order; those with a gradient: the embeddings, the others
+    std::vector<TableSlot> slots;      // `all` as the host copies take it
     int64_t total = 0, emb_total = 0, small_total = 0;
     int64_t t = 0;             // the optimiser's step counter
     int64_t no_negative_user = -1;   // the first user with stored entries and no admissible negative
@@ -500,6 +501,7 @@ static void ncf_layout(cornac_hip_ncf_t h) {
         if (!neumf) { N.logit_w = lw; N.logit_b = lb; }
     }
     h->total = off;
+    for (int q = 0; q < T.n; ++q) h->slots.push_back({T.t[q].off, T.t[q].rows, T.t[q].cols, false});
     h->emb.n = h->small.n = 0;
     h->emb_total = h->small_total = 0;
     for (int q = 0; q < T.n; ++q) {
@@ -585,29 +587,11 @@ int cornac_hip_ncf_n_tables(cornac_hip_ncf_t h, int *n) {
     });
 }
 
-static void ncf_put(cornac_hip_ncf_t h, DevBuf<float> &buf, const float *const *tables) {
-    for (int q = 0; q < h->all.n; ++q) {
-        if (!tables[q]) continue;
-        const NcfTable &t = h->all.t[q];
-        HIP_CHECK(hipMemcpyAsync(buf.p + t.off, tables[q], (size_t)(t.rows * t.cols) * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
-static void ncf_get(cornac_hip_ncf_t h, const DevBuf<float> &buf, float *const *tables) {
-    for (int q = 0; q < h->all.n; ++q) {
-        if (!tables[q]) continue;
-        const NcfTable &t = h->all.t[q];
-        HIP_CHECK(hipMemcpyAsync(tables[q], buf.p + t.off, (size_t)(t.rows * t.cols) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
 int cornac_hip_ncf_set_params(cornac_hip_ncf_t h, const float *const *tables) {
     return guarded([&] {
         check_handle(h, "NCF handle");
         REQUIRE(tables != nullptr, "%s: tables is NULL", ncf_name(h));
-        ncf_put(h, h->w, tables);
+        put_tables(h->stream, h->w.p, h->slots, tables);
     });
 }
 
@@ -615,15 +599,15 @@ int cornac_hip_ncf_get_params(cornac_hip_ncf_t h, float *const *tables) {
     return guarded([&] {
         check_handle(h, "NCF handle");
         REQUIRE(tables != nullptr, "%s: tables is NULL", ncf_name(h));
-        ncf_get(h, h->w, tables);
+        get_tables(h->stream, h->w.p, h->slots, tables);
     });
 }
 
 int cornac_hip_ncf_get_state(cornac_hip_ncf_t h, float *const *s1, float *const *s2, int64_t *t) {
     return guarded([&] {
         check_handle(h, "NCF handle");
-        if (s1) ncf_get(h, h->s1, s1);
-        if (s2) ncf_get(h, h->s2, s2);
+        if (s1) get_tables(h->stream, h->s1.p, h->slots, s1);
+        if (s2) get_tables(h->stream, h->s2.p, h->slots, s2);
         if (t) *t = h->t;
     });
 }
@@ -631,9 +615,7 @@ int cornac_hip_ncf_get_state(cornac_hip_ncf_t h, float *const *s1, float *const 
 int cornac_hip_ncf_reset_optimizer(cornac_hip_ncf_t h) {
     return guarded([&] {
         check_handle(h, "NCF handle");
-        HIP_CHECK(hipMemsetAsync(h->s1.p, 0, h->s1.n * sizeof(float), h->stream));
-        HIP_CHECK(hipMemsetAsync(h->s2.p, 0, h->s2.n * sizeof(float), h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        zero_state(h->stream, {&h->s1, &h->s2});
         h->t = 0;
     });
 }

@@ -326,6 +326,7 @@ struct cornac_hip_ngcf : ModelHandle {
     std::unique_ptr<NgcfLayer[]> layers;   // [L] (the buffers do not move)
     DevBuf<float> crow;              // the rows' weight sums
     DevBuf<float> w, m, v, grad;     // the parameter buffer, Adam's state, the gradient
+    std::vector<TableSlot> slots;    // the two tables and each layer's W1, b1, W2, b2 in w / m / v
     DevBuf<float> E, GE;             // [N x D]: the concatenated embeddings and the gradient at them
     DevBuf<float> GZ, T, R, gya, gyb;   // [N x max_d]: backward scratch
     DevBuf<float> wpart;             // [chunks x max_seg]: the weight and bias gradients' partials
@@ -434,6 +435,12 @@ int cornac_hip_ngcf_create(cornac_hip_ngcf_t *out, int device, int64_t n_users, 
         }
         h->D = off;
         h->n_params = at;
+        h->slots = {{0, n_users, emb_size, false}, {n_users * emb_size, n_items, emb_size, false}};
+        for (int l = 0; l < num_layers; ++l) {
+            const NgcfLayer &y = h->layers[(size_t)l];
+            h->slots.insert(h->slots.end(), {{y.oW1, y.dout, y.din, false}, {y.ob1, 1, y.dout, false},
+                                             {y.oW2, y.dout, y.din, false}, {y.ob2, 1, y.dout, false}});
+        }
         h->chunks = (N + kNgcfWgradRows - 1) / kNgcfWgradRows;
         const std::vector<float> crow = h->g.row_sums();
         h->open(device);
@@ -464,45 +471,27 @@ int cornac_hip_ngcf_create(cornac_hip_ngcf_t *out, int device, int64_t n_users, 
 
 int cornac_hip_ngcf_destroy(cornac_hip_ngcf_t h) { return destroy_handle(h); }
 
-// the tables and the layers' W1, b1, W2, b2 (layers [4 L], NULL entries and a NULL array skip) between `buf` and the host
-template <class F>
-static void ngcf_each(cornac_hip_ngcf_t h, F &&f, const void *user, const void *item, const void *const *layers) {
-    f((int64_t)0, h->n_users * h->d0, user);
-    f(h->n_users * h->d0, h->n_items * h->d0, item);
-    for (int l = 0; layers && l < h->L; ++l) {
-        const NgcfLayer &y = h->layers[(size_t)l];
-        f(y.oW1, (int64_t)y.dout * y.din, layers[4 * l]);
-        f(y.ob1, (int64_t)y.dout, layers[4 * l + 1]);
-        f(y.oW2, (int64_t)y.dout * y.din, layers[4 * l + 2]);
-        f(y.ob2, (int64_t)y.dout, layers[4 * l + 3]);
-    }
-}
-
-static void ngcf_put(cornac_hip_ngcf_t h, DevBuf<float> &buf, const float *user, const float *item, const float *const *layers) {
-    ngcf_each(h, [&](int64_t at, int64_t n, const void *host) {
-        if (host) HIP_CHECK(hipMemcpyAsync(buf.p + at, host, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    }, user, item, (const void *const *)layers);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-}
-
-static void ngcf_get(cornac_hip_ngcf_t h, const DevBuf<float> &buf, float *user, float *item, float *const *layers) {
-    ngcf_each(h, [&](int64_t at, int64_t n, const void *host) {
-        if (host) HIP_CHECK(hipMemcpyAsync(const_cast<void *>(host), buf.p + at, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    }, user, item, (const void *const *)layers);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+// the exported calls' user, item and layers [4 L] (a NULL array skips every layer) as one pointer list in the slots' order
+template <class T>
+static std::vector<T *> ngcf_list(cornac_hip_ngcf_t h, T *user, T *item, T *const *layers) {
+    std::vector<T *> p(h->slots.size(), nullptr);
+    p[0] = user;
+    p[1] = item;
+    if (layers) std::copy(layers, layers + 4 * h->L, p.begin() + 2);
+    return p;
 }
 
 int cornac_hip_ngcf_set_params(cornac_hip_ngcf_t h, const float *user, const float *item, const float *const *layers) {
     return guarded([&] {
         check_handle(h, "ngcf handle");
-        ngcf_put(h, h->w, user, item, layers);
+        put_tables(h->stream, h->w.p, h->slots, ngcf_list(h, user, item, layers).data());
     });
 }
 
 int cornac_hip_ngcf_get_params(cornac_hip_ngcf_t h, float *user, float *item, float *const *layers) {
     return guarded([&] {
         check_handle(h, "ngcf handle");
-        ngcf_get(h, h->w, user, item, layers);
+        get_tables(h->stream, h->w.p, h->slots, ngcf_list(h, user, item, layers).data());
     });
 }
 
@@ -510,8 +499,8 @@ int cornac_hip_ngcf_get_state(cornac_hip_ngcf_t h, float *m_user, float *m_item,
                               float *const *v_layers, int64_t *t) {
     return guarded([&] {
         check_handle(h, "ngcf handle");
-        ngcf_get(h, h->m, m_user, m_item, m_layers);
-        ngcf_get(h, h->v, v_user, v_item, v_layers);
+        get_tables(h->stream, h->m.p, h->slots, ngcf_list(h, m_user, m_item, m_layers).data());
+        get_tables(h->stream, h->v.p, h->slots, ngcf_list(h, v_user, v_item, v_layers).data());
         if (t) *t = h->t;
     });
 }
@@ -519,9 +508,7 @@ int cornac_hip_ngcf_get_state(cornac_hip_ngcf_t h, float *m_user, float *m_item,
 int cornac_hip_ngcf_reset_optimizer(cornac_hip_ngcf_t h) {
     return guarded([&] {
         check_handle(h, "ngcf handle");
-        HIP_CHECK(hipMemsetAsync(h->m.p, 0, h->m.n * sizeof(float), h->stream));
-        HIP_CHECK(hipMemsetAsync(h->v.p, 0, h->v.n * sizeof(float), h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        zero_state(h->stream, {&h->m, &h->v});
         h->t = 0;
     });
 }

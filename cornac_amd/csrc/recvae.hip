@@ -39,7 +39,7 @@ namespace chip {
 namespace {
 
 constexpr int kRvMaxK = 256, kRvMaxH = 1024, kRvMaxBatch = 1024;
-constexpr int kRvLayers = 5, kRvEncTables = 24, kRvTrainTables = 26, kRvTables = 53;
+constexpr int kRvLayers = 5, kRvEncTables = 24, kRvTables = 53;
 constexpr int kRvPerThread = kRvMaxH / kVaeBlock;
 constexpr int kRvChunk = 512;   // entries of a row per workgroup of the input layer
 constexpr float kRvLnEps = 0.1f, kRvLog2Pi = 1.8378770664093453f;
@@ -341,6 +341,9 @@ struct cornac_hip_recvae : ModelHandle {
     int k = 0, h = 0;
     int64_t t_enc = 0, t_dec = 0;   // the two Adams' step counters
     RvLayout L{};
+    // in the reference's state_dict order: the encoder's 24 tables (of w / m / v, and of `old` from 0), the three prior rows of
+    // `pri`, and decoder.weight / decoder.bias of w / m / v
+    std::vector<TableSlot> enc, prior, dec;
     DevCsr rows;                     // pointers and indices (values live in x / xn as float32)
     DevBuf<float> x, xn, sumx;       // the stored ratings, the L2-normalised ones, the rows' sums
     DevBuf<int64_t> col_ptr, col_ent;
@@ -366,32 +369,10 @@ struct cornac_hip_recvae : ModelHandle {
     float *S() { return act.p + (size_t)(5 * kRvLayers + 1) * (size_t)cap * (size_t)h; }
 };
 
-// encoder table q (0 .. 23) of a layout: offset, rows, columns in the reference's shape
-static void rv_enc_table(cornac_hip_recvae_t h, int q, int64_t *off, int64_t *rows, int64_t *cols) {
-    const RvLayout &L = h->L;
-    const int64_t I = h->n_items, hh = h->h, k = h->k;
-    if (q < 4 * kRvLayers) {
-        const int l = q / 4, r = q % 4;
-        *off = r == 0 ? L.W[l] : r == 1 ? L.b[l] : r == 2 ? L.g[l] : L.c[l];
-        *rows = r == 0 ? hh : 1;
-        *cols = r == 0 ? (l == 0 ? I : hh) : hh;
-    } else {
-        const int r = q - 4 * kRvLayers;
-        *off = r == 0 ? L.Wm : r == 1 ? L.bm : r == 2 ? L.Wv : L.bv;
-        *rows = r % 2 == 0 ? k : 1;
-        *cols = r % 2 == 0 ? hh : k;
-    }
-}
-
 // the 26 trainable tables (encoder's 24, decoder.weight, decoder.bias) of `buf` (w, m or v) to the host
 static void rv_get_trainable(cornac_hip_recvae_t h, const DevBuf<float> &buf, float *const *tables) {
-    for (int q = 0; q < kRvTrainTables; ++q) {
-        if (!tables[q]) continue;
-        int64_t off, rows, cols;
-        if (q < kRvEncTables) rv_enc_table(h, q, &off, &rows, &cols);
-        else { off = q == kRvEncTables ? h->L.Wd : h->L.bd; rows = q == kRvEncTables ? h->n_items : 1; cols = q == kRvEncTables ? h->k : h->n_items; }
-        get_table(h->stream, buf.p + off, tables[q], rows, cols, q == 0);
-    }
+    get_tables(h->stream, buf.p, h->enc, tables);
+    get_tables(h->stream, buf.p, h->dec, tables + kRvEncTables);
 }
 
 static void rv_ensure(cornac_hip_recvae_t h, int64_t cap) {
@@ -462,20 +443,27 @@ int cornac_hip_recvae_create(cornac_hip_recvae_t *out, int device, int64_t n_use
         {
             RvLayout &L = h->L;
             int64_t at = 0;
+            // the next table, rows x cols in the reference's shape (the first layer's weight is [h x I] there, [I x h] here)
+            auto add = [&](std::vector<TableSlot> &slots, int64_t rows, int64_t cols, bool transposed = false) {
+                slots.push_back({at, rows, cols, transposed});
+                at += rows * cols;
+                return slots.back().off;
+            };
             for (int l = 0; l < kRvLayers; ++l) {
-                L.W[l] = at; at += (l == 0 ? I : hh) * hh;
-                L.b[l] = at; at += hh;
-                L.g[l] = at; at += hh;
-                L.c[l] = at; at += hh;
+                L.W[l] = add(h->enc, hh, l == 0 ? I : hh, l == 0);
+                L.b[l] = add(h->enc, 1, hh);
+                L.g[l] = add(h->enc, 1, hh);
+                L.c[l] = add(h->enc, 1, hh);
             }
-            L.Wm = at; at += kk * hh;
-            L.bm = at; at += kk;
-            L.Wv = at; at += kk * hh;
-            L.bv = at; at += kk;
+            L.Wm = add(h->enc, kk, hh);
+            L.bm = add(h->enc, 1, kk);
+            L.Wv = add(h->enc, kk, hh);
+            L.bv = add(h->enc, 1, kk);
             L.enc_total = at;
-            L.Wd = at; at += I * kk;
-            L.bd = at; at += I;
+            L.Wd = add(h->dec, I, kk);
+            L.bd = add(h->dec, 1, I);
             L.total = at;
+            for (int64_t q = 0; q < 3; ++q) h->prior.push_back({q * kk, 1, kk, false});
         }
         for (DevBuf<float> *b : {&h->w, &h->m, &h->v}) {
             alloc_named(*b, (size_t)h->L.total, "RecVAE", "the tables and Adam's moments");
@@ -541,24 +529,12 @@ int cornac_hip_recvae_set_params(cornac_hip_recvae_t h, const float *const *tabl
     return guarded([&] {
         check_handle(h, "RecVAE handle");
         REQUIRE(tables != nullptr, "RecVAE: tables is NULL");
-        for (int q = 0; q < kRvTables; ++q) {
-            if (!tables[q]) continue;
-            int64_t off, rows, cols;
-            if (q < kRvEncTables) {
-                rv_enc_table(h, q, &off, &rows, &cols);
-                put_table(h->stream, h->w.p + off, tables[q], rows, cols, q == 0);
-            } else if (q < kRvEncTables + 3) {
-                put_table(h->stream, h->pri.p + (int64_t)(q - kRvEncTables) * h->k, tables[q], 1, h->k, false);   // (read per step)
-            } else if (q < 2 * kRvEncTables + 3) {
-                rv_enc_table(h, q - kRvEncTables - 3, &off, &rows, &cols);
-                put_table(h->stream, h->old.p + off, tables[q], rows, cols, q == kRvEncTables + 3);
-                h->post_stale = true;
-            } else if (q == kRvTables - 2) {
-                put_table(h->stream, h->w.p + h->L.Wd, tables[q], h->n_items, h->k, false);
-            } else {
-                put_table(h->stream, h->w.p + h->L.bd, tables[q], 1, h->n_items, false);
-            }
-        }
+        const float *const *old = tables + kRvEncTables + 3;
+        put_tables(h->stream, h->w.p, h->enc, tables);
+        put_tables(h->stream, h->pri.p, h->prior, tables + kRvEncTables);   // (read per step)
+        put_tables(h->stream, h->old.p, h->enc, old);
+        put_tables(h->stream, h->w.p, h->dec, tables + kRvTables - 2);
+        if (std::any_of(old, old + kRvEncTables, [](const float *t) { return t != nullptr; })) h->post_stale = true;
     });
 }
 
@@ -566,20 +542,10 @@ int cornac_hip_recvae_get_params(cornac_hip_recvae_t h, float *const *tables) {
     return guarded([&] {
         check_handle(h, "RecVAE handle");
         REQUIRE(tables != nullptr, "RecVAE: tables is NULL");
-        float *train[kRvTrainTables];
-        for (int q = 0; q < kRvEncTables; ++q) train[q] = tables[q];
-        train[kRvEncTables] = tables[kRvTables - 2];
-        train[kRvEncTables + 1] = tables[kRvTables - 1];
-        rv_get_trainable(h, h->w, train);
-        for (int q = 0; q < 3; ++q)
-            if (tables[kRvEncTables + q]) get_table(h->stream, h->pri.p + (int64_t)q * h->k, tables[kRvEncTables + q], 1, h->k, false);
-        for (int q = 0; q < kRvEncTables; ++q) {
-            float *dst = tables[kRvEncTables + 3 + q];
-            if (!dst) continue;
-            int64_t off, rows, cols;
-            rv_enc_table(h, q, &off, &rows, &cols);
-            get_table(h->stream, h->old.p + off, dst, rows, cols, q == 0);
-        }
+        get_tables(h->stream, h->w.p, h->enc, tables);
+        get_tables(h->stream, h->pri.p, h->prior, tables + kRvEncTables);
+        get_tables(h->stream, h->old.p, h->enc, tables + kRvEncTables + 3);
+        get_tables(h->stream, h->w.p, h->dec, tables + kRvTables - 2);
     });
 }
 
@@ -596,9 +562,7 @@ int cornac_hip_recvae_get_state(cornac_hip_recvae_t h, float *const *m, float *c
 int cornac_hip_recvae_reset_optimizer(cornac_hip_recvae_t h) {
     return guarded([&] {
         check_handle(h, "RecVAE handle");
-        HIP_CHECK(hipMemsetAsync(h->m.p, 0, h->m.n * sizeof(float), h->stream));
-        HIP_CHECK(hipMemsetAsync(h->v.p, 0, h->v.n * sizeof(float), h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        zero_state(h->stream, {&h->m, &h->v});
         h->t_enc = h->t_dec = 0;
     });
 }

@@ -1,12 +1,14 @@
 // Host scaffold of the models that score from a device handle of their own: named device allocation, CSR validation /
-// transpose / upload, the handle's device and stream, and the id-checked chunk loop of their score_users / score_pairs
-// entry points.  Included by knn.hip and ease.hip, and through vae_host.h by vaecf.hip, bivae.hip,
+// transpose / upload, the handle's device and stream, the map from a named table to its place in a device buffer with the one
+// copy path of set_params / get_params / get_state and the reset of the optimiser state, and the id-checked chunk loop of
+// their score_users / score_pairs entry points.  Included by knn.hip and ease.hip, and through vae_host.h by vaecf.hip, bivae.hip,
 // recvae.hip, ncf.hip and graph.h (lightgcn.hip, ngcf.hip).  Host code only; every message carries the model's prefix.
 #pragma once
 #include "common.h"
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 
 namespace chip {
 
@@ -121,6 +123,62 @@ int destroy_handle(H *h) {
     if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
     delete h;
     return CORNAC_HIP_OK;
+}
+
+// One named table of a handle model: where it starts in a device buffer (the parameters, or an optimiser-state buffer of the
+// same layout) and its shape on the host, rows x cols.  transposed: the device holds it [cols x rows] (a first layer's weight,
+// one row per input id).  A handle lists its tables once, in create, in the reference's state_dict order.
+struct TableSlot {
+    int64_t off, rows, cols;
+    bool transposed;
+};
+
+// dst [cols x rows] <- the transpose of src [rows x cols]
+inline void transpose_table(const float *src, int64_t rows, int64_t cols, float *dst) {
+    for (int64_t j = 0; j < rows; ++j)
+        for (int64_t i = 0; i < cols; ++i) dst[i * rows + j] = src[j * cols + i];
+}
+
+// host -> device copy of the tables of `slots` into the buffer at `base`; host[q] is slot q's table in the host's shape, and a
+// NULL entry skips it.  Returns with every copy done: one wait, until which the transposed tables' staging lives.
+inline void put_tables(hipStream_t stream, float *base, const std::vector<TableSlot> &slots, const float *const *host) {
+    std::vector<std::vector<float>> staged;
+    for (size_t q = 0; q < slots.size(); ++q) {
+        if (!host[q]) continue;
+        const TableSlot &s = slots[q];
+        const float *src = host[q];
+        if (s.transposed) {
+            staged.emplace_back((size_t)(s.rows * s.cols));
+            transpose_table(src, s.rows, s.cols, staged.back().data());
+            src = staged.back().data();
+        }
+        HIP_CHECK(hipMemcpyAsync(base + s.off, src, (size_t)(s.rows * s.cols) * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// device -> host, the same way: the transposed tables are turned once the one wait is over
+inline void get_tables(hipStream_t stream, const float *base, const std::vector<TableSlot> &slots, float *const *host) {
+    std::vector<std::vector<float>> staged(slots.size());
+    for (size_t q = 0; q < slots.size(); ++q) {
+        if (!host[q]) continue;
+        const TableSlot &s = slots[q];
+        float *dst = host[q];
+        if (s.transposed) {
+            staged[q].resize((size_t)(s.rows * s.cols));
+            dst = staged[q].data();
+        }
+        HIP_CHECK(hipMemcpyAsync(dst, base + s.off, (size_t)(s.rows * s.cols) * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (size_t q = 0; q < slots.size(); ++q)
+        if (host[q] && slots[q].transposed) transpose_table(staged[q].data(), slots[q].cols, slots[q].rows, host[q]);
+}
+
+// reset_optimizer's device half: the optimiser-state buffers back to zero, done on return (the step counters are the caller's)
+inline void zero_state(hipStream_t stream, std::initializer_list<DevBuf<float> *> buffers) {
+    for (DevBuf<float> *b : buffers) HIP_CHECK(hipMemsetAsync(b->p, 0, b->n * sizeof(float), stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 // the arguments of score_users (items == NULL) / score_pairs against the handle's sizes

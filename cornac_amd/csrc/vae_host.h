@@ -1,7 +1,7 @@
 // Host side of vae_device.h: torch.optim.Adam's coefficients at a step, the launch grids, the launchers of the tiled product
-// (a Linear layer's forward, its backward in the input, Adam on its weight, the split-range partial sums) and the copy of
-// one table between the host's shape and the device's.  Included by vaecf.hip, bivae.hip and recvae.hip; ncf.hip and graph.h
-// (lightgcn.hip, ngcf.hip) take adam_at and grid.  Host code only; a refusal carries the model's prefix.
+// (a Linear layer's forward, its backward in the input, Adam on its weight, the split-range partial sums).  Included by
+// vaecf.hip, bivae.hip and recvae.hip; ncf.hip and graph.h (lightgcn.hip, ngcf.hip) take adam_at and grid.  Host code only; a
+// refusal carries the model's prefix.
 #pragma once
 #include "sparse_model.h"
 #include "vae_device.h"
@@ -53,31 +53,6 @@ inline void weight_adam(hipStream_t stream, const char *model, const float *Gy, 
                         float *m, float *v, const VaeAdam &ad) {
     vae_gemm_kernel<false, false, 2><<<dim3(tiles(model, N, K)), kVaeBlock, 0, stream>>>(Gy, 1, N, X, K, 1, N, K, nb, nb + kVaeTk, w, nullptr,
                                                                                         nullptr, m, v, ad);
-}
-
-// host <-> device copy of one table [rows x cols] in the host's shape; transposed: the device holds it [cols x rows] (a first
-// layer's weight, one row per input id).  Both return with the copy done.
-inline void put_table(hipStream_t stream, float *dev, const float *host, int64_t rows, int64_t cols, bool transposed) {
-    std::vector<float> t;
-    if (transposed) {
-        t.resize((size_t)(rows * cols));
-        for (int64_t j = 0; j < rows; ++j)
-            for (int64_t i = 0; i < cols; ++i) t[(size_t)(i * rows + j)] = host[j * cols + i];
-        host = t.data();
-    }
-    HIP_CHECK(hipMemcpyAsync(dev, host, (size_t)(rows * cols) * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-}
-
-inline void get_table(hipStream_t stream, const float *dev, float *host, int64_t rows, int64_t cols, bool transposed) {
-    const size_t n = (size_t)(rows * cols);
-    std::vector<float> t;
-    if (transposed) t.resize(n);
-    HIP_CHECK(hipMemcpyAsync(transposed ? t.data() : host, dev, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    if (transposed)
-        for (int64_t j = 0; j < rows; ++j)
-            for (int64_t i = 0; i < cols; ++i) host[j * cols + i] = t[(size_t)(i * rows + j)];
 }
 
 }  // namespace

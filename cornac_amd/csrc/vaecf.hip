@@ -258,6 +258,7 @@ struct cornac_hip_vaecf : ModelHandle {
     int k = 0, h = 0, act = 0, lik = 0;
     int64_t t = 0;   // Adam's step counter
     VaeLayout L{};
+    std::vector<TableSlot> slots;   // the ten tables of w / m / v in the reference's state_dict order
     DevCsr rows, cols;   // the binarised X and its transpose: no values
     DevBuf<float> w, m, v, eps, loss;
     // per call, sized for `cap` rows
@@ -266,13 +267,6 @@ struct cornac_hip_vaecf : ModelHandle {
     int64_t kchunk = 0;
     DevBuf<float> h1, d1, mu, sd, z, h2, d2, kl, logits, part, ga2, gmu, glv, ga1, out;
 };
-
-static void vae_table_dims(cornac_hip_vaecf_t h, int64_t off[10], int64_t rows[10], int64_t cols[10]) {
-    const int64_t I = h->n_items, hh = h->h, k = h->k;
-    const int64_t o[10] = {h->L.W1, h->L.b1, h->L.Wm, h->L.bm, h->L.Wv, h->L.bv, h->L.D0, h->L.c0, h->L.D1, h->L.c1};
-    const int64_t r[10] = {hh, 1, k, 1, k, 1, hh, 1, I, 1}, c[10] = {I, hh, hh, k, hh, k, k, hh, hh, I};
-    for (int q = 0; q < 10; ++q) { off[q] = o[q]; rows[q] = r[q]; cols[q] = c[q]; }
-}
 
 static void vae_ensure(cornac_hip_vaecf_t h, int64_t cap) {
     if (cap <= h->cap) return;
@@ -310,6 +304,9 @@ int cornac_hip_vaecf_create(cornac_hip_vaecf_t *out, int device, int64_t n_users
             VaeLayout &L = h->L;
             L.W1 = 0; L.b1 = L.W1 + I * hh; L.Wm = L.b1 + hh; L.bm = L.Wm + kk * hh; L.Wv = L.bm + kk; L.bv = L.Wv + kk * hh;
             L.D0 = L.bv + kk; L.c0 = L.D0 + hh * kk; L.D1 = L.c0 + hh; L.c1 = L.D1 + I * hh; L.total = L.c1 + I;
+            // in the reference's shapes: W1 is [h x I] there, [I x h] here
+            h->slots = {{L.W1, hh, I, true}, {L.b1, 1, hh, false}, {L.Wm, kk, hh, false}, {L.bm, 1, kk, false}, {L.Wv, kk, hh, false},
+                        {L.bv, 1, kk, false}, {L.D0, hh, kk, false}, {L.c0, 1, hh, false}, {L.D1, I, hh, false}, {L.c1, 1, I, false}};
         }
         for (DevBuf<float> *b : {&h->w, &h->m, &h->v}) {
             alloc_named(*b, (size_t)h->L.total, "VAECF", "the tables and Adam's moments");
@@ -326,26 +323,11 @@ int cornac_hip_vaecf_create(cornac_hip_vaecf_t *out, int device, int64_t n_users
 
 int cornac_hip_vaecf_destroy(cornac_hip_vaecf_t h) { return destroy_handle(h); }
 
-// host <-> device copies of the ten tables of one buffer, in the reference's shapes (W1 is [h x I] there, [I x h] here)
-static void vae_put(cornac_hip_vaecf_t h, DevBuf<float> &buf, const float *const *tables) {
-    int64_t off[10], rows[10], cols[10];
-    vae_table_dims(h, off, rows, cols);
-    for (int q = 0; q < 10; ++q)
-        if (tables[q]) put_table(h->stream, buf.p + off[q], tables[q], rows[q], cols[q], q == 0);
-}
-
-static void vae_get(cornac_hip_vaecf_t h, const DevBuf<float> &buf, float *const *tables) {
-    int64_t off[10], rows[10], cols[10];
-    vae_table_dims(h, off, rows, cols);
-    for (int q = 0; q < 10; ++q)
-        if (tables[q]) get_table(h->stream, buf.p + off[q], tables[q], rows[q], cols[q], q == 0);
-}
-
 int cornac_hip_vaecf_set_params(cornac_hip_vaecf_t h, const float *const *tables) {
     return guarded([&] {
         check_handle(h, "VAECF handle");
         REQUIRE(tables != nullptr, "VAECF: tables is NULL");
-        vae_put(h, h->w, tables);
+        put_tables(h->stream, h->w.p, h->slots, tables);
     });
 }
 
@@ -353,15 +335,15 @@ int cornac_hip_vaecf_get_params(cornac_hip_vaecf_t h, float *const *tables) {
     return guarded([&] {
         check_handle(h, "VAECF handle");
         REQUIRE(tables != nullptr, "VAECF: tables is NULL");
-        vae_get(h, h->w, tables);
+        get_tables(h->stream, h->w.p, h->slots, tables);
     });
 }
 
 int cornac_hip_vaecf_get_state(cornac_hip_vaecf_t h, float *const *m, float *const *v, int64_t *t) {
     return guarded([&] {
         check_handle(h, "VAECF handle");
-        if (m) vae_get(h, h->m, m);
-        if (v) vae_get(h, h->v, v);
+        if (m) get_tables(h->stream, h->m.p, h->slots, m);
+        if (v) get_tables(h->stream, h->v.p, h->slots, v);
         if (t) *t = h->t;
     });
 }
@@ -369,9 +351,7 @@ int cornac_hip_vaecf_get_state(cornac_hip_vaecf_t h, float *const *m, float *con
 int cornac_hip_vaecf_reset_optimizer(cornac_hip_vaecf_t h) {
     return guarded([&] {
         check_handle(h, "VAECF handle");
-        HIP_CHECK(hipMemsetAsync(h->m.p, 0, h->m.n * sizeof(float), h->stream));
-        HIP_CHECK(hipMemsetAsync(h->v.p, 0, h->v.n * sizeof(float), h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        zero_state(h->stream, {&h->m, &h->v});
         h->t = 0;
     });
 }

@@ -26,23 +26,16 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from .recommender import Recommender, ScoreException
+from .recommender import Recommender, ScoreException, filled_handle, float32_tables
 
 NAMES = ("feature_dict.user", "feature_dict.item")
 
 
-def _initial_tables(n_users, n_items, emb_size):
-    """lightgcn.py:72-82: xavier_uniform_ on torch.empty(n, emb_size) per node type, in the graph's ntypes order: item, user"""
-    import torch
-
-    item = torch.nn.init.xavier_uniform_(torch.empty(n_items, emb_size))
-    user = torch.nn.init.xavier_uniform_(torch.empty(n_users, emb_size))
-    return user.numpy().astype(np.float32).copy(), item.numpy().astype(np.float32).copy()
-
-
 class GraphRecommender(Recommender):
-    """What the two graph models (LightGCN, NGCF) share on the host: the train matrix over all nodes, the monitored value of
-    early stopping, and scoring from the learned embeddings `U` and `V` through the fused scorer with zero bases."""
+    """What the two graph models (LightGCN, NGCF) share on the host: the train matrix over all nodes, the epoch loop of `fit`,
+    the monitored value of early stopping, the propagation over a given graph after `load_state_dict`, and scoring from the
+    learned embeddings `U` and `V` through the fused scorer with zero bases.  A subclass supplies `_initial_params()` (drawn
+    with torch on the CPU), `_model(X, params)` (a device model over the matrix X that holds `params`) and `_take(model)`."""
 
     def _graph_matrix(self, train_set):
         """the train matrix over total_users x total_items (lightgcn.py:22-30), sorted indices"""
@@ -52,6 +45,57 @@ class GraphRecommender(Recommender):
         X.sum_duplicates()
         X.sort_indices()
         return X
+
+    def fit(self, train_set, val_set=None):
+        """recom_lightgcn.py:102-194, recom_ngcf.py:106-199: every fit starts from new parameters and a new optimiser, as there"""
+        Recommender.fit(self, train_set, val_set)
+        if not self.trainable:
+            return self
+        import torch
+
+        if self.seed is not None:
+            torch.manual_seed(self.seed)
+        init = self._initial_params()
+        model = self._model(self._graph_matrix(train_set), init)
+        try:
+            n_obs = len(train_set.uir_tuple[0])
+            self.loss_history = []
+            for epoch in range(int(self.num_epochs)):
+                bu, bi, bj, ptr = [], [], [], [0]
+                for u, i, j in train_set.uij_iter(batch_size=self.batch_size, shuffle=True):
+                    bu.append(u); bi.append(i); bj.append(j); ptr.append(ptr[-1] + len(u))
+                ptr = np.asarray(ptr, np.int64)
+                losses, _, _ = model.fit_epoch(ptr, np.concatenate(bu), np.concatenate(bi), np.concatenate(bj), self.learning_rate,
+                                               self.lambda_reg)
+                self.loss_history.append(float((losses * np.diff(ptr)).sum() / n_obs))   # recom_lightgcn.py:175-181
+                if self.verbose:
+                    print("%s epoch %d: loss %.6g" % (self.name, epoch + 1, self.loss_history[-1]))
+                if self.early_stopping is not None:   # the embeddings that the monitored value is computed from
+                    self._take(model)
+                    if self.early_stop(train_set, val_set, **self.early_stopping):
+                        break
+            if self.early_stopping is None or not self.loss_history:
+                self._take(model)
+        finally:
+            model.close()
+        return self
+
+    def _propagate_over(self, graph):
+        """`U` and `V` of `self.params` over `graph`: the train matrix over the tables' users x items, or a Dataset"""
+        shape = tuple(len(self.params["feature_dict." + n]) for n in ("user", "item"))
+        X = graph if sp.issparse(graph) else None
+        if X is None:
+            u, i, _ = graph.uir_tuple
+            X = sp.csr_matrix((np.ones(len(u)), (u, i)), shape=shape)
+        X = sp.csr_matrix(X)
+        X.sort_indices()
+        if X.shape != shape:
+            raise ValueError("the graph is %r, expected %r" % (X.shape, shape))
+        model = self._model(X, self.params)
+        try:
+            self.U, self.V = model.propagate()
+        finally:
+            model.close()
 
     def monitor_value(self, train_set, val_set):
         """Recall@20 on the validation set (recom_lightgcn.py:196-227; section 4.1.2 of the paper); None without one"""
@@ -114,41 +158,17 @@ class LightGCN(GraphRecommender):
         self.seed = seed
         self.device = device
 
-    # ---- fit ----------------------------------------------------------------------------------------
-    def fit(self, train_set, val_set=None):
-        """recom_lightgcn.py:102-194: every fit starts from new tables and a new optimiser, as there"""
-        Recommender.fit(self, train_set, val_set)
-        if not self.trainable:
-            return self
+    def _initial_params(self):
+        """lightgcn.py:72-82: xavier_uniform_ on torch.empty(n, emb_size) per node type, in the graph's ntypes order: item, user"""
         import torch
 
-        if self.seed is not None:
-            torch.manual_seed(self.seed)
-        user, item = _initial_tables(self.total_users, self.total_items, int(self.emb_size))
-        model = _lib.LightGcnModel(self._graph_matrix(train_set), int(self.emb_size), int(self.num_layers), device=self.device)
-        try:
-            model.set_params(user, item)
-            n_obs = len(train_set.uir_tuple[0])
-            self.loss_history = []
-            for epoch in range(int(self.num_epochs)):
-                bu, bi, bj, ptr = [], [], [], [0]
-                for u, i, j in train_set.uij_iter(batch_size=self.batch_size, shuffle=True):
-                    bu.append(u); bi.append(i); bj.append(j); ptr.append(ptr[-1] + len(u))
-                ptr = np.asarray(ptr, np.int64)
-                losses, _, _ = model.fit_epoch(ptr, np.concatenate(bu), np.concatenate(bi), np.concatenate(bj), self.learning_rate,
-                                               self.lambda_reg)
-                self.loss_history.append(float((losses * np.diff(ptr)).sum() / n_obs))   # recom_lightgcn.py:175-181
-                if self.verbose:
-                    print("%s epoch %d: loss %.6g" % (self.name, epoch + 1, self.loss_history[-1]))
-                if self.early_stopping is not None:   # the tables that the monitored value is computed from
-                    self._take(model)
-                    if self.early_stop(train_set, val_set, **self.early_stopping):
-                        break
-            if self.early_stopping is None or not self.loss_history:
-                self._take(model)
-        finally:
-            model.close()
-        return self
+        item = torch.nn.init.xavier_uniform_(torch.empty(self.total_items, int(self.emb_size)))
+        user = torch.nn.init.xavier_uniform_(torch.empty(self.total_users, int(self.emb_size)))
+        return OrderedDict(zip(NAMES, (user.numpy().astype(np.float32).copy(), item.numpy().astype(np.float32).copy())))
+
+    def _model(self, X, params):
+        model = _lib.LightGcnModel(X, int(self.emb_size), int(self.num_layers), device=self.device)
+        return filled_handle(model, lambda m: m.set_params(params[NAMES[0]], params[NAMES[1]]))
 
     def _take(self, model):
         """the layer-0 tables and the final embeddings from the device (recom_lightgcn.py:184-189)"""
@@ -166,10 +186,7 @@ class LightGCN(GraphRecommender):
         """layer-0 tables (arrays or torch tensors) under the reference's names.  The final embeddings depend on the graph:
         with `graph` (the train matrix over total_users x total_items, or a Dataset) they are propagated on the device;
         without it `U` and `V` stay as they are."""
-        tabs = {}
-        for n, a in state.items():
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
+        tabs = float32_tables(state)
         if set(tabs) != set(NAMES):
             raise KeyError("state_dict needs exactly the keys %r" % (NAMES,))
         user, item = tabs[NAMES[0]], tabs[NAMES[1]]
@@ -179,18 +196,5 @@ class LightGCN(GraphRecommender):
         self.emb_size = int(user.shape[1])
         self.params = OrderedDict(zip(NAMES, (user, item)))
         if graph is not None:
-            X = graph if sp.issparse(graph) else None
-            if X is None:
-                u, i, _ = graph.uir_tuple
-                X = sp.csr_matrix((np.ones(len(u)), (u, i)), shape=(user.shape[0], item.shape[0]))
-            X = sp.csr_matrix(X)
-            X.sort_indices()
-            if X.shape != (user.shape[0], item.shape[0]):
-                raise ValueError("the graph is %r, expected %r" % (X.shape, (user.shape[0], item.shape[0])))
-            model = _lib.LightGcnModel(X, self.emb_size, int(self.num_layers), device=self.device)
-            try:
-                model.set_params(user, item)
-                self.U, self.V = model.propagate()
-            finally:
-                model.close()
+            self._propagate_over(graph)
         self._drop_scorer()

@@ -30,7 +30,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint
+from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint, check_table_shapes, filled_handle, float32_tables
 
 
 def _f32(t):
@@ -198,10 +198,7 @@ class _NCF(HandleScoredRecommender):
 
     def load_state_dict(self, state):
         """tables (arrays or torch tensors) under the reference's names; shapes must agree with each other"""
-        tabs = OrderedDict()
-        for n, a in state.items():
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
+        tabs = float32_tables(state)
         try:
             n_users, n_items, f, layers = self._shape_from(tabs)
         except (KeyError, IndexError):
@@ -209,10 +206,7 @@ class _NCF(HandleScoredRecommender):
         names = _lib.NcfModel.NAMES(self.KIND, layers)
         if set(tabs) != set(names):
             raise KeyError("state_dict needs exactly the keys %r" % (names,))
-        want = _lib.NcfModel.shapes(self.KIND, n_users, n_items, f, layers)
-        for n in names:
-            if tabs[n].shape != want[n]:
-                raise ValueError("%s has shape %r, expected %r" % (n, tabs[n].shape, want[n]))
+        check_table_shapes(tabs, _lib.NcfModel.shapes(self.KIND, n_users, n_items, f, layers))
         if self.KIND != "MLP":
             self.num_factors = f
         if self.KIND != "GMF":
@@ -221,10 +215,6 @@ class _NCF(HandleScoredRecommender):
         self._drop_scorer()
 
     # ---- prediction ---------------------------------------------------------------------------------
-    def _drop_scorer(self):
-        HandleScoredRecommender._drop_scorer(self)
-        self.__dict__.pop("_rank_tables", None)
-
     def _handle_key(self):
         return tuple(_table_fingerprint(self.params[n]) for n in self._names())
 
@@ -232,12 +222,7 @@ class _NCF(HandleScoredRecommender):
         """scoring needs the tables alone: the handle gets a matrix without entries"""
         n_users, n_items = self._shape_from(self.params)[:2]
         model = self._new_model(sp.csr_matrix((n_users, n_items), dtype=np.float64))
-        try:
-            model.set_params(self.params)
-        except Exception:
-            model.close()
-            raise
-        return model
+        return filled_handle(model, lambda m: m.set_params(self.params))
 
 
 class GMF(_NCF):

@@ -26,38 +26,17 @@ import os
 from collections import OrderedDict
 
 import numpy as np
-import scipy.sparse as sp
 
 from . import _lib
 from .lightgcn import GraphRecommender
-from .recommender import Recommender
-
-
-def _initial_params(n_users, n_items, emb_size, layer_sizes):
-    """ngcf.py:40-60, 119-148 in the reference's draw order, under its state_dict names"""
-    import torch
-
-    out, din = OrderedDict(), int(emb_size)
-    for l, dout in enumerate(int(x) for x in layer_sizes):
-        W1, W2 = torch.nn.Linear(din, dout, bias=True), torch.nn.Linear(din, dout, bias=True)
-        torch.nn.init.xavier_uniform_(W1.weight)
-        torch.nn.init.constant_(W1.bias, 0)
-        torch.nn.init.xavier_uniform_(W2.weight)
-        torch.nn.init.constant_(W2.bias, 0)
-        for n, lin in (("W1", W1), ("W2", W2)):
-            out["layers.%d.%s.weight" % (l, n)] = lin.weight.detach().numpy().astype(np.float32).copy()
-            out["layers.%d.%s.bias" % (l, n)] = lin.bias.detach().numpy().astype(np.float32).copy()
-        din = dout
-    out["feature_dict.item"] = torch.nn.init.xavier_uniform_(torch.empty(n_items, emb_size)).numpy().astype(np.float32).copy()
-    out["feature_dict.user"] = torch.nn.init.xavier_uniform_(torch.empty(n_users, emb_size)).numpy().astype(np.float32).copy()
-    return out
+from .recommender import filled_handle, float32_tables
 
 
 class NGCF(GraphRecommender):
     """Parameters are the reference's (recom_ngcf.py:27-104): `emb_size`, `layer_sizes`, `dropout_rates`, `num_epochs`,
     `learning_rate`, `batch_size`, `early_stopping` ({min_delta, patience} on Recall@20 of the validation set), `lambda_reg`,
-    `seed`; plus `device`, the HIP device ordinal.  The graph matrix, the monitored value, the scoring through the fused scorer
-    with zero bases and the ANN accessors are `GraphRecommender`'s, shared with LightGCN."""
+    `seed`; plus `device`, the HIP device ordinal.  The graph matrix, the epoch loop of `fit`, the monitored value, the scoring
+    through the fused scorer with zero bases and the ANN accessors are `GraphRecommender`'s, shared with LightGCN."""
 
     def __init__(self, name="NGCF", emb_size=64, layer_sizes=[64, 64, 64], dropout_rates=[0.1, 0.1, 0.1], num_epochs=1000,
                  learning_rate=0.001, batch_size=1024, early_stopping=None, lambda_reg=1e-4, trainable=True, verbose=False, seed=2020,
@@ -74,45 +53,30 @@ class NGCF(GraphRecommender):
         self.seed = seed
         self.device = device
 
-    def _model(self, X):
-        assert len(self.layer_sizes) == len(self.dropout_rates), "'layer_sizes' and 'dropout_rates' must be of the same size"
-        key = int.from_bytes(os.urandom(8), "little") if self.seed is None else int(self.seed)
-        return _lib.NgcfModel(X, int(self.emb_size), list(self.layer_sizes), list(self.dropout_rates), dropout_key=key, device=self.device)
-
-    def fit(self, train_set, val_set=None):
-        """recom_ngcf.py:106-199: every fit starts from new parameters and a new optimiser, as there"""
-        Recommender.fit(self, train_set, val_set)
-        if not self.trainable:
-            return self
+    def _initial_params(self):
+        """ngcf.py:40-60, 119-148 in the reference's draw order, under its state_dict names"""
         import torch
 
-        if self.seed is not None:
-            torch.manual_seed(self.seed)
-        init = _initial_params(self.total_users, self.total_items, int(self.emb_size), self.layer_sizes)
-        model = self._model(self._graph_matrix(train_set))
-        try:
-            model.set_params(init)
-            n_obs = len(train_set.uir_tuple[0])
-            self.loss_history = []
-            for epoch in range(int(self.num_epochs)):
-                bu, bi, bj, ptr = [], [], [], [0]
-                for u, i, j in train_set.uij_iter(batch_size=self.batch_size, shuffle=True):
-                    bu.append(u); bi.append(i); bj.append(j); ptr.append(ptr[-1] + len(u))
-                ptr = np.asarray(ptr, np.int64)
-                losses, _, _ = model.fit_epoch(ptr, np.concatenate(bu), np.concatenate(bi), np.concatenate(bj), self.learning_rate,
-                                               self.lambda_reg)
-                self.loss_history.append(float((losses * np.diff(ptr)).sum() / n_obs))   # recom_ngcf.py:180-186
-                if self.verbose:
-                    print("%s epoch %d: loss %.6g" % (self.name, epoch + 1, self.loss_history[-1]))
-                if self.early_stopping is not None:   # the embeddings that the monitored value is computed from
-                    self._take(model)
-                    if self.early_stop(train_set, val_set, **self.early_stopping):
-                        break
-            if self.early_stopping is None or not self.loss_history:
-                self._take(model)
-        finally:
-            model.close()
-        return self
+        out, din = OrderedDict(), int(self.emb_size)
+        for l, dout in enumerate(int(x) for x in self.layer_sizes):
+            W1, W2 = torch.nn.Linear(din, dout, bias=True), torch.nn.Linear(din, dout, bias=True)
+            torch.nn.init.xavier_uniform_(W1.weight)
+            torch.nn.init.constant_(W1.bias, 0)
+            torch.nn.init.xavier_uniform_(W2.weight)
+            torch.nn.init.constant_(W2.bias, 0)
+            for n, lin in (("W1", W1), ("W2", W2)):
+                out["layers.%d.%s.weight" % (l, n)] = lin.weight.detach().numpy().astype(np.float32).copy()
+                out["layers.%d.%s.bias" % (l, n)] = lin.bias.detach().numpy().astype(np.float32).copy()
+            din = dout
+        for n, count in (("item", self.total_items), ("user", self.total_users)):
+            out["feature_dict." + n] = torch.nn.init.xavier_uniform_(torch.empty(count, self.emb_size)).numpy().astype(np.float32).copy()
+        return out
+
+    def _model(self, X, params):
+        assert len(self.layer_sizes) == len(self.dropout_rates), "'layer_sizes' and 'dropout_rates' must be of the same size"
+        key = int.from_bytes(os.urandom(8), "little") if self.seed is None else int(self.seed)
+        model = _lib.NgcfModel(X, int(self.emb_size), list(self.layer_sizes), list(self.dropout_rates), dropout_key=key, device=self.device)
+        return filled_handle(model, lambda m: m.set_params(params))
 
     def _take(self, model):
         """the parameters and the eval-mode embeddings from the device (recom_ngcf.py:189-194)"""
@@ -129,10 +93,7 @@ class NGCF(GraphRecommender):
         """parameters (arrays or torch tensors) under the reference's names; the layer sizes are read from them.  The embeddings
         depend on the graph: with `graph` (the train matrix over total_users x total_items, or a Dataset) they are propagated on
         the device; without it `U` and `V` stay as they are."""
-        tabs = {}
-        for n, a in state.items():
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
+        tabs = float32_tables(state)
         n_layers = len([n for n in tabs if n.endswith(".W1.weight")])
         if n_layers < 1 or "feature_dict.user" not in tabs or "feature_dict.item" not in tabs:
             raise KeyError("state_dict needs feature_dict.user, feature_dict.item and at least layers.0.*")
@@ -152,18 +113,5 @@ class NGCF(GraphRecommender):
             self.dropout_rates = [0.0] * n_layers
         self.params = OrderedDict((n, tabs[n]) for n in shapes)
         if graph is not None:
-            X = graph if sp.issparse(graph) else None
-            if X is None:
-                u, i, _ = graph.uir_tuple
-                X = sp.csr_matrix((np.ones(len(u)), (u, i)), shape=(user.shape[0], item.shape[0]))
-            X = sp.csr_matrix(X)
-            X.sort_indices()
-            if X.shape != (user.shape[0], item.shape[0]):
-                raise ValueError("the graph is %r, expected %r" % (X.shape, (user.shape[0], item.shape[0])))
-            model = self._model(X)
-            try:
-                model.set_params(self.params)
-                self.U, self.V = model.propagate()
-            finally:
-                model.close()
+            self._propagate_over(graph)
         self._drop_scorer()

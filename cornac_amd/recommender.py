@@ -15,6 +15,7 @@ import json
 import os
 import pickle
 import warnings
+from collections import OrderedDict
 from datetime import datetime
 from glob import glob
 
@@ -87,6 +88,34 @@ def _table_fingerprint(a):
     n = flat.size
     probe = flat[:: max(1, n // _PROBE)][:_PROBE].tobytes() if n else b""
     return (id(a), a.shape, a.dtype.num, hash(probe))
+
+
+def float32_tables(state, names=None):
+    """the tables of a `state` mapping (arrays or torch tensors; all of them, or `names` in that order) as float32 C-contiguous
+    copies under their names"""
+    out = OrderedDict()
+    for n in state if names is None else names:
+        a = state[n]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        out[n] = np.ascontiguousarray(a, np.float32).copy()
+    return out
+
+
+def check_table_shapes(tabs, want):
+    """ValueError for the first table of `want` (name -> shape) that `tabs` holds in another shape"""
+    for n, shape in want.items():
+        if tabs[n].shape != shape:
+            raise ValueError("%s has shape %r, expected %r" % (n, tabs[n].shape, shape))
+
+
+def filled_handle(model, fill):
+    """the new device model `model` once fill(model) has set its tables; closed again if that fails"""
+    try:
+        fill(model)
+    except Exception:
+        model.close()
+        raise
+    return model
 
 
 def clip(values, lower_bound, upper_bound):
@@ -489,7 +518,7 @@ class HandleScoredRecommender(Recommender):
         raise NotImplementedError
 
     def _build_handle(self):
-        """a new handle holding what `_handle_key()` describes (closed again if filling it fails)"""
+        """a new handle holding what `_handle_key()` describes (`filled_handle` closes it again if filling it fails)"""
         raise NotImplementedError
 
     def _user_rows(self, handle, users):
@@ -517,6 +546,7 @@ class HandleScoredRecommender(Recommender):
         Recommender._drop_scorer(self)
         handle = self.__dict__.pop(self._HANDLE_ATTRS[0], None)
         self.__dict__.pop(self._HANDLE_ATTRS[1], None)
+        self.__dict__.pop("_rank_tables", None)   # (what a subclass's _scoring_tables caches from the handle)
         if handle is not None:
             handle.close()
 

@@ -29,7 +29,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint
+from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint, check_table_shapes, filled_handle, float32_tables
 
 
 class RecVAE(HandleScoredRecommender):
@@ -180,17 +180,10 @@ class RecVAE(HandleScoredRecommender):
         """tables (arrays or torch tensors) under the reference's names; shapes must agree with each other"""
         if set(state) != set(self.NAMES):
             raise KeyError("state_dict needs exactly the keys %r" % (self.NAMES,))
-        tabs = OrderedDict()
-        for n in self.NAMES:
-            a = state[n]
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
+        tabs = float32_tables(state, self.NAMES)
         hidden, n_items = tabs["encoder.fc1.weight"].shape
         latent = tabs["encoder.fc_mu.weight"].shape[0]
-        want = _lib.RecvaeModel.shapes(n_items, hidden, latent)
-        for n in self.NAMES:
-            if tabs[n].shape != want[n]:
-                raise ValueError("%s has shape %r, expected %r" % (n, tabs[n].shape, want[n]))
+        check_table_shapes(tabs, _lib.RecvaeModel.shapes(n_items, hidden, latent))
         self.recvae = tabs
         self.hidden_dim, self.latent_dim = hidden, latent
         self._drop_scorer()
@@ -201,23 +194,13 @@ class RecVAE(HandleScoredRecommender):
     batch_num_items = Recommender.batch_num_items
     register_exclusions = Recommender.register_exclusions
 
-    def _drop_scorer(self):
-        HandleScoredRecommender._drop_scorer(self)
-        self.__dict__.pop("_rank_tables", None)
-
     def _handle_key(self):
         X = self.r_mat
         return (id(X),) + tuple(_table_fingerprint(a) for a in (X.indptr, X.indices, X.data)) + tuple(
             _table_fingerprint(self.recvae[n]) for n in self.NAMES)
 
     def _build_handle(self):
-        model = self._model(self.r_mat)
-        try:
-            model.set_params(self.recvae)
-        except Exception:
-            model.close()
-            raise
-        return model
+        return filled_handle(self._model(self.r_mat), lambda m: m.set_params(self.recvae))
 
     def _scoring_tables(self):
         """(mu of every user, decoder.weight, decoder.bias, zeros): the decoder's logits as a factor model"""

@@ -19,7 +19,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
-from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint
+from .recommender import HandleScoredRecommender, Recommender, _table_fingerprint, check_table_shapes, filled_handle, float32_tables
 
 
 class VAECF(HandleScoredRecommender):
@@ -116,17 +116,10 @@ class VAECF(HandleScoredRecommender):
         """tables (arrays or torch tensors) under the reference's names; shapes must agree with each other"""
         if set(state) != set(self.NAMES):
             raise KeyError("state_dict needs exactly the keys %r" % (self.NAMES,))
-        tabs = OrderedDict()
-        for n in self.NAMES:
-            a = state[n]
-            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            tabs[n] = np.ascontiguousarray(a, np.float32).copy()
+        tabs = float32_tables(state, self.NAMES)
         h, n_items = tabs[self.NAMES[0]].shape
         k = tabs[self.NAMES[2]].shape[0]
-        want = _lib.VaecfModel.shapes(n_items, k, h)
-        for n in self.NAMES:
-            if tabs[n].shape != want[n]:
-                raise ValueError("%s has shape %r, expected %r" % (n, tabs[n].shape, want[n]))
+        check_table_shapes(tabs, _lib.VaecfModel.shapes(n_items, k, h))
         self.vae = tabs
         self.k, self.autoencoder_structure = k, [h]
         self._drop_scorer()
@@ -137,10 +130,6 @@ class VAECF(HandleScoredRecommender):
     batch_num_items = Recommender.batch_num_items
     register_exclusions = Recommender.register_exclusions
 
-    def _drop_scorer(self):
-        HandleScoredRecommender._drop_scorer(self)
-        self.__dict__.pop("_rank_tables", None)
-
     def _handle_key(self):
         X = self.r_mat
         return (id(X),) + tuple(_table_fingerprint(a) for a in (X.indptr, X.indices)) + tuple(
@@ -148,12 +137,7 @@ class VAECF(HandleScoredRecommender):
 
     def _build_handle(self):
         model = _lib.VaecfModel(self.r_mat, self.k, self._check_structure(), self.act_fn, self.likelihood, device=self.device)
-        try:
-            model.set_params(self.vae)
-        except Exception:
-            model.close()
-            raise
-        return model
+        return filled_handle(model, lambda m: m.set_params(self.vae))
 
     def _scoring_tables(self):
         """(h2 of every user at z = mu, D1, c1, zeros): the decoder's logits as a factor model"""
